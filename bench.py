@@ -6,9 +6,12 @@ synthetic shell-R NeRF pairs at 128^3 (BASELINE.json configs[1]: batch 4 pairs =
 MFMA with fp32 accumulate / fp32 master weights).  With --gpus N the driver launches N ranks through
 torch.distributed.run; every rank takes its own 4 pairs (weak scaling) and gradients are averaged over RCCL.
 
-Prints ONE JSON line on rank 0 (see the contract in the repo brief): value = pairs/s over all ranks,
-plus "roofline" for the dominant kernel (HIP-event timed inside the timed region) and "cpu_baseline"
-(the oracle = PyTorch-CPU restatement of the reference, timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0: value = pairs/s over all ranks, ms_per_step = wall time of one timed step.
+A plain run sets up, warms up, times --steps steps and prints that line, nothing else.  --full adds everything
+else the line reports: "roofline" for the dominant kernel (HIP-event timed inside the timed region), the
+multi-rank self-check, the dense-head, NeRF-label, NGP and end-to-end figures, and "cpu_baseline" (the
+oracle = PyTorch-CPU restatement of the reference, timed on this box's host cores on a bounded sample).
+--dump-outputs DIR writes what the last timed step computed as .npy files (same arguments, same inputs).
 """
 import argparse
 import json
@@ -51,7 +54,39 @@ def parse():
     ap.add_argument("--chain-serial", action="store_true", help="--chain: also time the serial chain of rounds 3-5 on the same blocks")
     ap.add_argument("--chain-scenes", type=int, default=16, help="--chain: scenes (pairs of blocks) per pass")
     ap.add_argument("--ngp-radius", type=float, default=1.0, help="--ngp: occupied cells = ball of this radius in the [-1.5,1.5]^3 block")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="the default line with every figure beside the headline (roofline, rank self-check, "
+                                                        "dense head, NeRF labels, NGP, end-to-end chain, CPU baseline); --kernel-report and --occupancy-sweep imply it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (default line only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.ngp or args.eval or args.nerf_labels or args.chain):
+        ap.error("--dump-outputs applies to the default training-step line")
+    if args.kernel_report or args.occupancy_sweep:      # parts of the full measurement
+        args.full = True
+    return args
+
+
+def dump_outputs(path: str, result: dict, preds, opt, n_param_sample: int = 1 << 21):
+    """--dump-outputs: what TrainStep.step returned in the last timed step (its losses and clipped gradient norm), the predictions it made
+    for every pair (pose, overlap scores and predicted correspondences of every decoder layer) and a fixed, seeded sample of the updated
+    parameters (the whole flat buffer is ~245 MB), as float32 DIR/<name>.npy, at most 64 MB in all."""
+    import numpy as np
+    arrays = {f"loss_{k}": v for k, v in result["losses"].items()}
+    arrays["grad_norm"] = result["grad_norm"]
+    for i, p in enumerate(preds):
+        for k in ("pose", "src_overlap", "tgt_overlap", "src_kp_warped", "tgt_kp_warped"):
+            arrays[f"pair{i}_{k}"] = p[k][0] if isinstance(p[k], list) else p[k]
+    n = opt.n_active
+    idx = torch.randint(0, n, (min(n_param_sample, n),), generator=torch.Generator().manual_seed(0)).sort().values
+    arrays["params_sample"] = opt.flat_p[idx.to(opt.flat_p.device)]
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py --dump-outputs: {total / 2**20:.1f} MB of outputs, more than 64 MB (fewer --pairs)")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(res: int, target_res: int, samples: int = 3):
@@ -604,25 +639,27 @@ def main():
         for _ in range(args.warmup):
             ts.step(batch)
         sync()
-        if ts._sync is not None:
-            ts._sync.measure_exposed = True
-            ts._sync.exposed_ms()
-        ops.PROFILER = ops.KernelTimer()
-        # (both native executors bracket their own convolution / linear launches with HIP events while the profiler is enabled)
+        if args.full:
+            if ts._sync is not None:
+                ts._sync.measure_exposed = True
+                ts._sync.exposed_ms()
+            ops.PROFILER = ops.KernelTimer()
+            # (both native executors bracket their own convolution / linear launches with HIP events while the profiler is enabled)
         t0 = time.perf_counter()
         for i in range(args.steps):
-            if i == args.event_steps:      # HIP-event brackets on the first steps of the timed region only (they cost host time)
+            if i == args.event_steps and ops.PROFILER is not None:      # HIP-event brackets on the first steps of the timed region only (they cost host time)
                 ops.PROFILER.enabled = False
-            ts.step(batch)
+            last = ts.step(batch)
         sync()
         el = time.perf_counter() - t0
         pr, ops.PROFILER = ops.PROFILER, None
-        model.drain_trunk_timings(pr)   # the native trunk executor's own HIP-event records of the same region
+        if pr is not None:
+            model.drain_trunk_timings(pr)   # the native trunk executor's own HIP-event records of the same region
         if world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, pr
+        return el, pr, last
 
     peak = MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else 157.3
 
@@ -677,26 +714,29 @@ def main():
 
     # the second, dense-head measurement keeps the BASELINE.md FLOP accounting (8.5 TFLOP per pair) comparable
     dense = None
-    if not args.dense_head and args.precision == "bf16" and not args.no_dense_reference:
-        el_d, pr_d = timed(False)
+    if args.full and not args.dense_head and args.precision == "bf16" and not args.no_dense_reference:
+        el_d, pr_d, _ = timed(False)
         if rank == 0:
             rf_d, _ = roofline_of(pr_d, "dense_head")
             dense = {"value": args.pairs * world * args.steps / el_d, "unit": "pairs/s", "ms_per_step": 1e3 * el_d / args.steps, "roofline": rf_d}
-    elapsed, prof = timed(not args.dense_head and args.precision == "bf16")
-    # the multi-rank run validates itself: identical parameters and the same clipped gradient norm on every rank after the timed steps, and how long
-    # the step stream stood still for gradient exchange that backward did not hide (trivially in sync / 0 ms at one rank)
-    from dreg_nerf_amd.optim import ranks_in_sync
-    in_sync = ranks_in_sync(ts.optimizer, ts.optimizer.grad_norm())
-    exposed = ts._sync.exposed_ms() if ts._sync is not None else (0.0, 0)
-    if ts._sync is not None:
-        ts._sync.measure_exposed = False
-    if world > 1:
-        t_ = torch.tensor([exposed[0]], dtype=torch.float64, device=dev)
-        dist.all_reduce(t_, op=dist.ReduceOp.MAX)
-        exposed = (float(t_.item()), exposed[1])
-    if not in_sync["ranks_in_sync"] and rank == 0:
-        # reported in the line (`ranks_in_sync`: false) and loudly here; the throughput of an out-of-sync run must not be read as a DDP measurement
-        print(f"bench.py: RANKS OUT OF SYNC after the timed region: {in_sync}", file=sys.stderr, flush=True)
+    elapsed, prof, last = timed(not args.dense_head and args.precision == "bf16")
+    if args.dump_outputs and rank == 0:       # before anything below steps the model further
+        dump_outputs(args.dump_outputs, last, ts.last_preds, ts.optimizer)
+    if args.full:
+        # the multi-rank run validates itself: identical parameters and the same clipped gradient norm on every rank after the timed steps, and how long
+        # the step stream stood still for gradient exchange that backward did not hide (trivially in sync / 0 ms at one rank)
+        from dreg_nerf_amd.optim import ranks_in_sync
+        in_sync = ranks_in_sync(ts.optimizer, ts.optimizer.grad_norm())
+        exposed = ts._sync.exposed_ms() if ts._sync is not None else (0.0, 0)
+        if ts._sync is not None:
+            ts._sync.measure_exposed = False
+        if world > 1:
+            t_ = torch.tensor([exposed[0]], dtype=torch.float64, device=dev)
+            dist.all_reduce(t_, op=dist.ReduceOp.MAX)
+            exposed = (float(t_.item()), exposed[1])
+        if not in_sync["ranks_in_sync"] and rank == 0:
+            # reported in the line (`ranks_in_sync`: false) and loudly here; the throughput of an out-of-sync run must not be read as a DDP measurement
+            print(f"bench.py: RANKS OUT OF SYNC after the timed region: {in_sync}", file=sys.stderr, flush=True)
 
     # the active-set head's work follows the occupied surface: the same step on shells of 1e4 .. 1e5 occupied voxels per side
     sweep = None
@@ -730,7 +770,7 @@ def main():
     # the same step with its overlap labels ray-marched from the pairs' NeRF blocks, as on real data (train_nerf_regtr.py:186-199): an extra,
     # clearly separate figure next to the headline (whose labels are synthetic, like every other input)
     with_labels = None
-    if world == 1 and args.precision == "bf16" and args.res == 128 and not args.dense_head and not args.no_nerf_labels_reference:
+    if args.full and world == 1 and args.precision == "bf16" and args.res == 128 and not args.dense_head and not args.no_nerf_labels_reference:
         try:
             import shutil
             td, paths = write_generated_blocks(2 * args.pairs, 50, 0)
@@ -754,12 +794,6 @@ def main():
         except Exception as e:      # never lose the headline line to the extra figure
             with_labels = {"error": repr(e)[:300]}
     if rank == 0:
-        roofline, by_label = roofline_of(prof, "dense_head" if args.dense_head else "active_set")
-        if args.kernel_report:
-            with open(args.kernel_report, "w") as f:
-                f.write("kernel\tshape\tcalls\ttotal_ms\tavg_ms\tTFLOP/s\n")
-                for (n, l), (c, m, fl) in sorted(by_label.items(), key=lambda kv: -kv[1][1]):
-                    f.write(f"{n}\t{l}\t{c}\t{m:.3f}\t{m / c:.4f}\t{fl / (m * 1e-3) / 1e12 if m > 0 else 0:.1f}\n")
         pairs = args.pairs * world * args.steps
         out = {
             "metric": "nerf_pairs_per_sec_regtr_fwd_bwd_128", "value": pairs / elapsed, "unit": "pairs/s",
@@ -767,56 +801,62 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
-            "ranks_in_sync": in_sync["ranks_in_sync"], "rank_sync": in_sync,
-            "allreduce_exposed_ms_per_step": exposed[0], "allreduce_buckets": (len(ts._sync.buckets) if ts._sync is not None else 0),
             "config": {"workload": f"RegTR fwd+bwd+AdamW, shell-R synthetic pairs, {args.res}^3 grids, "
                                    f"{args.pairs} pairs ({2 * args.pairs} grids) per GPU per step, random-init weights",
                        "global_batch_pairs": args.pairs * world, "resolution": args.res,
                        "fpn_head": "dense" if args.dense_head else "active-set (identical results; rows around occupied voxels)",
                        "parallelism": f"dp{world}"},
-            "roofline": roofline,
         }
-        # the step as a whole against the same roof: every bracketed convolution / linear launch of the bracketed step (algorithmic
-        # FLOPs; stride-2 data gradients at 1/8 of the dense taps) + the point-set half's linear layers when they ran unbracketed
-        # (1,048,576 MAC per key point and encoder layer, 131,072 per decoder layer-row: SURVEY.md 8(d)), over the step's wall time
-        bracketed = sum(fl for (c, m, fl) in prof.summary(subtract_overhead=False)[0].values()) / max(min(args.event_steps, args.steps), 1)
-        lin = 0.0
-        if not args.kernel_report and getattr(model, "last_batched", None) is not None and args.precision == "bf16":
-            R = int(model.last_batched["xyz"].shape[0])
-            lin = 3.0 * 2.0 * R * 6 * (1048576 + 131072)
-        out["whole_step"] = {"algorithmic_TFLOP_per_step": (bracketed + lin) / 1e12, "achieved_TFLOPs": (bracketed + lin) / (elapsed / args.steps) / 1e12,
-                             "frac_of_mfma_roof": (bracketed + lin) / (elapsed / args.steps) / 1e12 / peak,
-                             "note": "convolutions + linear layers only (attention, BatchNorm, LayerNorm, optimizer excluded from the FLOPs, included in the time)"}
-        if dense is not None:
-            out["dense_head"] = dense
-        if sweep is not None:
-            out["occupancy_sweep"] = sweep
-        if with_labels is not None:
-            out["labels_from_nerf_blocks"] = with_labels
-        if world == 1 and not args.no_ngp_reference and args.precision == "bf16":
-            # BASELINE.json configs[3] beside the headline (the driver only runs the default line): NGP grid extraction of one 128^3 block,
-            # the same measurement as `python bench.py --ngp`, compact
-            try:
-                import copy
-                a2 = copy.copy(args)
-                a2.steps, a2.warmup, a2.ngp_windows = 40, 3, 5
-                ng = ngp_measure(a2, rank, world, dev)
-                rf_n = ng["roofline"]
-                out["ngp_config4"] = {"metric": ng["metric"], "value": ng["value"], "unit": ng["unit"], "ms_per_block": ng["ms_per_step"], "timed": "median of 5 windows of 40 blocks",
-                                      "points_per_block": ng["config"]["points_per_block"],
-                                      "roofline": {k: rf_n.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms")},
-                                      "density_query": {k: rf_n["density_kernel"].get(k) for k in ("kernel", "avg_launch_ms", "Gpts_per_s", "traffic", "gathered_over_hbm_bytes")},
-                                      **({"cpu_baseline": ng["cpu_baseline"]} if "cpu_baseline" in ng else {})}
-            except Exception as e:      # never lose the headline line to the extra figure
-                out["ngp_config4"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_ngp_reference and args.precision == "bf16" and args.res == 128:
-            try:
-                out["eval_end_to_end"] = eval_end_to_end(args, dev)
-            except Exception as e:      # never lose the headline line to the extra figure
-                out["eval_end_to_end"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
-            cres = args.cpu_res or (128 if (os.cpu_count() or 1) >= 32 else 64)
-            out["cpu_baseline"] = cpu_baseline(min(cres, args.res), args.res, args.cpu_samples)
+        if args.full:
+            roofline, by_label = roofline_of(prof, "dense_head" if args.dense_head else "active_set")
+            if args.kernel_report:
+                with open(args.kernel_report, "w") as f:
+                    f.write("kernel\tshape\tcalls\ttotal_ms\tavg_ms\tTFLOP/s\n")
+                    for (n, l), (c, m, fl) in sorted(by_label.items(), key=lambda kv: -kv[1][1]):
+                        f.write(f"{n}\t{l}\t{c}\t{m:.3f}\t{m / c:.4f}\t{fl / (m * 1e-3) / 1e12 if m > 0 else 0:.1f}\n")
+            out.update({"ranks_in_sync": in_sync["ranks_in_sync"], "rank_sync": in_sync, "allreduce_exposed_ms_per_step": exposed[0],
+                        "allreduce_buckets": (len(ts._sync.buckets) if ts._sync is not None else 0), "roofline": roofline})
+            # the step as a whole against the same roof: every bracketed convolution / linear launch of the bracketed step (algorithmic
+            # FLOPs; stride-2 data gradients at 1/8 of the dense taps) + the point-set half's linear layers when they ran unbracketed
+            # (1,048,576 MAC per key point and encoder layer, 131,072 per decoder layer-row: SURVEY.md 8(d)), over the step's wall time
+            bracketed = sum(fl for (c, m, fl) in prof.summary(subtract_overhead=False)[0].values()) / max(min(args.event_steps, args.steps), 1)
+            lin = 0.0
+            if not args.kernel_report and getattr(model, "last_batched", None) is not None and args.precision == "bf16":
+                R = int(model.last_batched["xyz"].shape[0])
+                lin = 3.0 * 2.0 * R * 6 * (1048576 + 131072)
+            out["whole_step"] = {"algorithmic_TFLOP_per_step": (bracketed + lin) / 1e12, "achieved_TFLOPs": (bracketed + lin) / (elapsed / args.steps) / 1e12,
+                                 "frac_of_mfma_roof": (bracketed + lin) / (elapsed / args.steps) / 1e12 / peak,
+                                 "note": "convolutions + linear layers only (attention, BatchNorm, LayerNorm, optimizer excluded from the FLOPs, included in the time)"}
+            if dense is not None:
+                out["dense_head"] = dense
+            if sweep is not None:
+                out["occupancy_sweep"] = sweep
+            if with_labels is not None:
+                out["labels_from_nerf_blocks"] = with_labels
+            if world == 1 and not args.no_ngp_reference and args.precision == "bf16":
+                # BASELINE.json configs[3] beside the headline: NGP grid extraction of one 128^3 block, the same measurement as
+                # `python bench.py --ngp`, compact
+                try:
+                    import copy
+                    a2 = copy.copy(args)
+                    a2.steps, a2.warmup, a2.ngp_windows = 40, 3, 5
+                    ng = ngp_measure(a2, rank, world, dev)
+                    rf_n = ng["roofline"]
+                    out["ngp_config4"] = {"metric": ng["metric"], "value": ng["value"], "unit": ng["unit"], "ms_per_block": ng["ms_per_step"], "timed": "median of 5 windows of 40 blocks",
+                                          "points_per_block": ng["config"]["points_per_block"],
+                                          "roofline": {k: rf_n.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms")},
+                                          "density_query": {k: rf_n["density_kernel"].get(k) for k in ("kernel", "avg_launch_ms", "Gpts_per_s", "traffic", "gathered_over_hbm_bytes")},
+                                          **({"cpu_baseline": ng["cpu_baseline"]} if "cpu_baseline" in ng else {})}
+                except Exception as e:      # never lose the headline line to the extra figure
+                    out["ngp_config4"] = {"error": repr(e)[:300]}
+            if world == 1 and not args.no_ngp_reference and args.precision == "bf16" and args.res == 128:
+                try:
+                    out["eval_end_to_end"] = eval_end_to_end(args, dev)
+                except Exception as e:      # never lose the headline line to the extra figure
+                    out["eval_end_to_end"] = {"error": repr(e)[:300]}
+            if world == 1 and not args.no_cpu_baseline:
+                cres = args.cpu_res or (128 if (os.cpu_count() or 1) >= 32 else 64)
+                out["cpu_baseline"] = cpu_baseline(min(cres, args.res), args.res, args.cpu_samples)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

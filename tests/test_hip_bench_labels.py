@@ -26,7 +26,7 @@ def _run_under_rocprof(tmp_path, tag, extra):
     if not os.path.exists(rocprof):
         pytest.skip("rocprofv3 not installed")
     env = dict(os.environ, TMPDIR=str(tmp_path))
-    cmd = [rocprof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", str(tmp_path / tag), "-o", "k", "--", sys.executable, os.path.join(ROOT, "bench.py"),
+    cmd = [rocprof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", str(tmp_path / tag), "-o", "k", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--full",
            "--no-cpu-baseline", "--no-dense-reference", "--no-nerf-labels-reference", "--no-ngp-reference"] + extra
     out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -99,3 +99,20 @@ def test_bench_eval_and_ngp_lines():
             assert 0.0 <= d["rre_deg_mean"] <= 180.0 and d["rte_mean"] >= 0.0
         elif "--ngp" in flags:
             assert d["roofline"]["density_kernel"]["avg_launch_ms"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """The plain default line times exactly --steps steps and carries the headline only (the extra figures are --full's); --dump-outputs
+    writes the last timed step's losses, gradient norm, per-pair predictions and parameter sample as float32 .npy files."""
+    import numpy as np
+    out = _run(["bench.py", "--res", "64", "--pairs", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=900)
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "nerf_pairs_per_sec_regtr_fwd_bwd_128" and d["unit"] == "pairs/s" and d["dtype"] == "bf16" and d["steps"] == 3
+    assert abs(d["value"] - 2 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "whole_step", "rank_sync", "dense_head", "cpu_baseline", "ngp_config4", "eval_end_to_end"} & set(d)
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert {"loss_total", "grad_norm", "params_sample", "pair0_pose", "pair1_pose", "pair1_tgt_overlap"} <= set(files)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20 and files["pair0_pose"].shape[-2:] == (3, 4)
