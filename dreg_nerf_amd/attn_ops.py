@@ -627,3 +627,69 @@ def weighted_kabsch_pairs(xyz, corr, ov, tab: "ProblemTable", eps: float = 1e-6)
     L.check(lib.dreg_weighted_kabsch_pairs(L.ptr(xyz), L.ptr(corr), L.ptr(ov), L.ptr(tab.pair_probs), L.ptr(out), P_, Ln, R, eps, L.stream()),
             "dreg_weighted_kabsch_pairs")
     return out
+
+
+class _KabschFn(torch.autograd.Function):
+    """weighted_kabsch with a backward: csrc/pointset.hip kabsch_bwd_kernel (closed form on the forward's own SVD, fp64)."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, eps):
+        a32, b32, w32 = a.detach().contiguous().float(), b.detach().contiguous().float(), w.detach().contiguous().float()
+        out = weighted_kabsch(a32, b32, w32, eps)
+        ctx.save_for_backward(a32, b32, w32)
+        ctx.eps = eps
+        ctx.dtypes = (a.dtype, b.dtype, w.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        ga = torch.empty_like(a) if need[0] else None
+        gb = torch.empty_like(b) if need[1] else None
+        gw = torch.empty_like(w) if need[2] else None
+        g = g.contiguous().float()
+        L.check(L.load().dreg_weighted_kabsch_bwd(L.ptr(a), L.ptr(b), L.ptr(w), L.ptr(g), L.ptr(ga), L.ptr(gb), L.ptr(gw), a.shape[0], a.shape[1],
+                                                  ctx.eps, L.stream()), "dreg_weighted_kabsch_bwd")
+        cast = lambda t, dt: t.to(dt) if t is not None else None
+        return cast(ga, ctx.dtypes[0]), cast(gb, ctx.dtypes[1]), cast(gw, ctx.dtypes[2]), None
+
+
+class _KabschPairsFn(torch.autograd.Function):
+    """weighted_kabsch_pairs with a backward into corr and ov (xyz: data, no gradient)."""
+
+    @staticmethod
+    def forward(ctx, xyz, corr, ov, tab, eps):
+        xyz32, corr32 = xyz.detach().contiguous().float(), corr.detach().contiguous().float()
+        ov32 = ov.detach().reshape(corr.shape[0], -1).contiguous().float()
+        out = weighted_kabsch_pairs(xyz32, corr32, ov32, tab, eps)
+        ctx.save_for_backward(xyz32, corr32, ov32)
+        ctx.tab, ctx.eps = tab, eps
+        ctx.ov_shape, ctx.dtypes = ov.shape, (corr.dtype, ov.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xyz, corr, ov = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gc = torch.empty_like(corr) if need[1] else None
+        go = torch.empty_like(ov) if need[2] else None
+        g = g.contiguous().float()
+        tab = ctx.tab
+        L.check(L.load().dreg_weighted_kabsch_pairs_bwd(L.ptr(xyz), L.ptr(corr), L.ptr(ov), L.ptr(tab.pair_probs), L.ptr(g), L.ptr(gc), L.ptr(go),
+                                                        len(tab.segs), corr.shape[0], xyz.shape[0], ctx.eps, L.stream()),
+                "dreg_weighted_kabsch_pairs_bwd")
+        gc = gc.to(ctx.dtypes[0]) if gc is not None else None
+        go = go.reshape(ctx.ov_shape).to(ctx.dtypes[1]) if go is not None else None
+        return None, gc, go, None, None
+
+
+def weighted_kabsch_grad(a, b, w, eps: float = 1e-6):
+    """weighted_kabsch inside autograd: a,b [P,N,3], w [P,N] -> [P,3,4] whose gradient reaches a, b and w (se3.py:89-140 differentiated)."""
+    return _KabschFn.apply(a, b, w, eps)
+
+
+def weighted_kabsch_pairs_grad(xyz, corr, ov, tab: "ProblemTable", eps: float = 1e-6):
+    """weighted_kabsch_pairs inside autograd: xyz [R,3], corr [L,R,3], ov [L,R] or [L,R,1] -> [P,L,3,4]; gradients reach corr and ov (ov's in the
+    shape it came in); xyz gets none."""
+    return _KabschPairsFn.apply(xyz, corr, ov, tab, eps)

@@ -50,6 +50,10 @@ def config_parser(argv=None):
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")
+    p.add_argument("--pose_loss_weight", type=float, default=0.0,
+                   help="train: weight of an opt-in pose loss (mean L1 of the source key points moved by the predicted vs the true pose); 0 = the reference's step")
+    p.add_argument("--pose_loss_layers", type=str, default="last", choices=["last", "all"],
+                   help="train: decoder layers the pose loss supervises (the reference's losses read the last one)")
     args, _unknown = p.parse_known_args(argv)
     if isinstance(args.aabb, str):
         args.aabb = [float(v) for v in args.aabb.split(",")]

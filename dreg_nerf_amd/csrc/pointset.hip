@@ -1,5 +1,5 @@
 // Row-wise / small kernels of the point-set half (gfx950): LayerNorm (+position embedding) forward/backward,
-// sine position embedding, overlap head (GEMV + sigmoid), ReLU backward, weighted Kabsch (3x3 SVD on device),
+// sine position embedding, overlap head (GEMV + sigmoid), ReLU backward, weighted Kabsch (3x3 SVD on device) and its backward,
 // voxel-average downsampling (sorted keys + segmented mean) and the flat AdamW / gradient-norm kernels.
 //
 // Reference call sites: conerf/register/transformer.py:238-293 (LayerNorm, with_pos_embed),
@@ -284,7 +284,10 @@ __global__ __launch_bounds__(256) void kabsch_pairs_kernel(const float* __restri
     KabschPair X{xyz, corr + (size_t)l * R * 3, ov + (size_t)l * R, pr[0], pr[1], pr[2]};
     kabsch_body(X, pr[1] + pr[3], out + (size_t)blockIdx.x * 12, eps);
 }
-template <typename Acc> __device__ void kabsch_body(const Acc& X, int N, float* __restrict__ o, float eps)
+// The forward's sums (every thread ends with all of them) and its SVD (one lane): shared by the solve and its backward, so that the backward
+// differentiates exactly the rotation the forward returned.
+struct KabschSums { double sw, norm, ca[3], cb[3], H[3][3]; };
+template <typename Acc> __device__ void kabsch_sums(const Acc& X, int N, float eps, KabschSums& S)
 {
     const int t = threadIdx.x;
     __shared__ double red[9][256];
@@ -329,35 +332,186 @@ template <typename Acc> __device__ void kabsch_body(const Acc& X, int N, float* 
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[r][c] += (X.a(i, r) - ca[r]) * (X.b(i, c) - cb[c]) * wn;
     }
     block_sums(&H[0][0], 9);
-    if (t == 0) {
-        // H = U S V^T.  Eigen-decompose H^T H = V S^2 V^T, sort descending, U = H V S^-1 (last column by cross product).
-        double HtH[3][3], V[3][3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += H[k][i] * H[k][j]; HtH[i][j] = s; }
-        jacobi_eig3(HtH, V);
-        double ev[3] = {HtH[0][0], HtH[1][1], HtH[2][2]};
-        int idx[3] = {0, 1, 2};
-        for (int i = 0; i < 2; ++i) for (int j = i + 1; j < 3; ++j) if (ev[idx[j]] > ev[idx[i]]) { int tmp = idx[i]; idx[i] = idx[j]; idx[j] = tmp; }
-        double Vs[3][3], U[3][3];
-        for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) Vs[k][j] = V[k][idx[j]];
-        for (int j = 0; j < 2; ++j) {
-            double n2 = 0;
-            for (int i = 0; i < 3; ++i) { double s = 0; for (int k = 0; k < 3; ++k) s += H[i][k] * Vs[k][j]; U[i][j] = s; n2 += s * s; }
-            const double n = sqrt(n2);
-            for (int i = 0; i < 3; ++i) U[i][j] = n > 0 ? U[i][j] / n : (i == j);
-        }
-        // third singular vectors from cross products so that det(U), det(V) are consistent with the two computed columns
-        double u2[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1], U[0][0] * U[1][1] - U[1][0] * U[0][1]};
-        double v2[3] = {Vs[1][0] * Vs[2][1] - Vs[2][0] * Vs[1][1], Vs[2][0] * Vs[0][1] - Vs[0][0] * Vs[2][1], Vs[0][0] * Vs[1][1] - Vs[1][0] * Vs[0][1]};
-        // R = V diag(1,1,d) U^T with d = +1 here gives det(R) = +1 by construction (both bases right-handed),
-        // which is exactly the reference's "flip the last column of V when det(V U^T) < 0" rule (se3.py:128-134).
-        double R[3][3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i][j] = Vs[i][0] * U[j][0] + Vs[i][1] * U[j][1] + v2[i] * u2[j];
+    S.sw = sw;
+    S.norm = norm;
+    for (int c = 0; c < 3; ++c) { S.ca[c] = ca[c]; S.cb[c] = cb[c]; }
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.H[r][c] = H[r][c];
+}
+// H = U S V^T.  Eigen-decompose H^T H = V S^2 V^T, sort descending, U = H V S^-1 (last column by cross product).  U, V come out right-handed.
+__device__ void kabsch_svd(const double (&H)[3][3], double (&U)[3][3], double (&Vs)[3][3])
+{
+    double HtH[3][3], V[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += H[k][i] * H[k][j]; HtH[i][j] = s; }
+    jacobi_eig3(HtH, V);
+    double ev[3] = {HtH[0][0], HtH[1][1], HtH[2][2]};
+    int idx[3] = {0, 1, 2};
+    for (int i = 0; i < 2; ++i) for (int j = i + 1; j < 3; ++j) if (ev[idx[j]] > ev[idx[i]]) { int tmp = idx[i]; idx[i] = idx[j]; idx[j] = tmp; }
+    for (int k = 0; k < 3; ++k) for (int j = 0; j < 3; ++j) Vs[k][j] = V[k][idx[j]];
+    for (int j = 0; j < 2; ++j) {
+        double n2 = 0;
+        for (int i = 0; i < 3; ++i) { double s = 0; for (int k = 0; k < 3; ++k) s += H[i][k] * Vs[k][j]; U[i][j] = s; n2 += s * s; }
+        const double n = sqrt(n2);
+        for (int i = 0; i < 3; ++i) U[i][j] = n > 0 ? U[i][j] / n : (i == j);
+    }
+    // third singular vectors from cross products so that det(U), det(V) are consistent with the two computed columns
+    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1]; U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1]; U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+    Vs[0][2] = Vs[1][0] * Vs[2][1] - Vs[2][0] * Vs[1][1]; Vs[1][2] = Vs[2][0] * Vs[0][1] - Vs[0][0] * Vs[2][1]; Vs[2][2] = Vs[0][0] * Vs[1][1] - Vs[1][0] * Vs[0][1];
+}
+// R = V diag(1,1,d) U^T with d = +1 here gives det(R) = +1 by construction (both bases right-handed),
+// which is exactly the reference's "flip the last column of V when det(V U^T) < 0" rule (se3.py:128-134).
+__device__ __forceinline__ void kabsch_rotation(const double (&U)[3][3], const double (&V)[3][3], double (&R)[3][3])
+{
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i][j] = V[i][0] * U[j][0] + V[i][1] * U[j][1] + V[i][2] * U[j][2];
+}
+template <typename Acc> __device__ void kabsch_body(const Acc& X, int N, float* __restrict__ o, float eps)
+{
+    KabschSums S;
+    kabsch_sums(X, N, eps, S);
+    if (threadIdx.x == 0) {
+        double U[3][3], V[3][3], R[3][3];
+        kabsch_svd(S.H, U, V);
+        kabsch_rotation(U, V, R);
         for (int i = 0; i < 3; ++i) {
-            double tr = cb[i];
-            for (int j = 0; j < 3; ++j) { o[i * 4 + j] = (float)R[i][j]; tr -= R[i][j] * ca[j]; }
+            double tr = S.cb[i];
+            for (int j = 0; j < 3; ++j) { o[i * 4 + j] = (float)R[i][j]; tr -= R[i][j] * S.ca[j]; }
             o[i * 4 + 3] = (float)tr;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ weighted Kabsch backward
+// Gradient of T = [R | t] (above) with respect to a, b, w, given dL/dT = g [3,4].  Closed form (fp64 on one lane), with sigma~_i = U_i^T H V_i (the third
+// one signed: negative exactly when the reference flips V) and R = V U^T:
+//   G = G_R - g_t ca^T,  g_ca = -R^T g_t,  g_cb = g_t,  Gh = V^T G U (= U^T R^T G U),  Y_ij = (Gh_ij - Gh_ji) / (sigma~_i + sigma~_j),  Y_ii = 0,
+//   Gbar = dL/dH = -U Y V^T (= -U Y U^T R^T).
+// The denominators are those of the polar factor, not torch's 1/(s_i^2 - s_j^2): finite when singular values repeat.  They vanish only when the rotation
+// is not determined by the data (rank <= 1, or s2 = s3 with the reflection fix): a pair (i, j) with |sigma~_i + sigma~_j| <= KABSCH_BWD_GUARD * sigma~_1
+// contributes nothing (Y_ij = 0) — below that ratio the rotation about that axis is below the fp32 inputs' own precision.  No NaN / Inf for finite inputs.
+// Per row, with wn = w_i / norm, da = a_i - ca, db = b_i - cb and m = sum(wn) - 1 (0 unless the weight sum was clamped to eps: then norm is a constant and
+// H = sum wn a b^T - (2 - sum wn) ca cb^T):
+//   pa = g_ca + m Gbar cb,  pb = g_cb + m Gbar^T ca
+//   g_a_i = wn (Gbar db + pa),  g_b_i = wn (Gbar^T da + pb),  g_w_i = (da^T Gbar db + da.pa + db.pb + c0) / norm
+//   c0 = -<Gbar, H>  (sum w >= eps: the weights' normalisation),  c0 = ca.g_ca + cb.g_cb + 2m ca^T Gbar cb  (clamped)
+constexpr double KABSCH_BWD_GUARD = 1e-6;
+struct KabschDenseGrad {   // any pointer may be null (skipped)
+    float* ga; float* gb; float* gw;
+    __device__ __forceinline__ void put(int i, const double (&a)[3], const double (&b)[3], double w) const {
+        if (ga) for (int c = 0; c < 3; ++c) ga[i * 3 + c] = (float)a[c];
+        if (gb) for (int c = 0; c < 3; ++c) gb[i * 3 + c] = (float)b[c];
+        if (gw) gw[i] = (float)w;
+    }
+};
+struct KabschPairGrad {    // source rows: corr is b; target rows: corr is a; ov is w in both (xyz are data: no gradient)
+    float* gcorr; float* gov; int s0, ns, t0;
+    __device__ __forceinline__ void put(int i, const double (&a)[3], const double (&b)[3], double w) const {
+        const size_t r = i < ns ? (size_t)(s0 + i) : (size_t)(t0 + i - ns);
+        const double* g = i < ns ? b : a;
+        if (gcorr) for (int c = 0; c < 3; ++c) gcorr[r * 3 + c] = (float)g[c];
+        if (gov) gov[r] = (float)w;
+    }
+};
+template <typename Acc, typename Out> __device__ void kabsch_bwd_body(const Acc& X, int N, const float* __restrict__ g, float eps, const Out& Y)
+{
+    const int t = threadIdx.x;
+    KabschSums S;
+    kabsch_sums(X, N, eps, S);
+    __shared__ double pub[16];     // Gbar [9], pa [3], pb [3], c0
+    if (t == 0) {
+        double U[3][3], V[3][3], R[3][3];
+        kabsch_svd(S.H, U, V);
+        kabsch_rotation(U, V, R);
+        double sig[3];
+        for (int k = 0; k < 3; ++k) {
+            double s = 0;
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) s += U[i][k] * S.H[i][j] * V[j][k];
+            sig[k] = s;
+        }
+        double G[3][3], gca[3], gcb[3];
+        for (int i = 0; i < 3; ++i) {
+            gcb[i] = g[i * 4 + 3];
+            for (int j = 0; j < 3; ++j) G[i][j] = g[i * 4 + j] - g[i * 4 + 3] * S.ca[j];
+        }
+        for (int i = 0; i < 3; ++i) gca[i] = -(R[0][i] * gcb[0] + R[1][i] * gcb[1] + R[2][i] * gcb[2]);
+        double GU[3][3], Gh[3][3], Yh[3][3], YV[3][3], Gb[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) GU[i][j] = G[i][0] * U[0][j] + G[i][1] * U[1][j] + G[i][2] * U[2][j];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Gh[i][j] = V[0][i] * GU[0][j] + V[1][i] * GU[1][j] + V[2][i] * GU[2][j];
+        const double tau = KABSCH_BWD_GUARD * sig[0];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double d = sig[i] + sig[j];
+                Yh[i][j] = (i == j || !(fabs(d) > tau)) ? 0.0 : (Gh[i][j] - Gh[j][i]) / d;
+            }
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) YV[i][j] = Yh[i][0] * V[j][0] + Yh[i][1] * V[j][1] + Yh[i][2] * V[j][2];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Gb[i][j] = -(U[i][0] * YV[0][j] + U[i][1] * YV[1][j] + U[i][2] * YV[2][j]);
+        const bool clamped = !(S.sw >= (double)eps);
+        const double m = clamped ? S.sw / S.norm - 1.0 : 0.0;
+        double c0 = 0;
+        for (int i = 0; i < 3; ++i) {
+            double gcbv = 0, gtca = 0;
+            for (int j = 0; j < 3; ++j) { gcbv += Gb[i][j] * S.cb[j]; gtca += Gb[j][i] * S.ca[j]; }
+            pub[9 + i] = gca[i] + m * gcbv;
+            pub[12 + i] = gcb[i] + m * gtca;
+            for (int j = 0; j < 3; ++j) pub[i * 3 + j] = Gb[i][j];
+            c0 += clamped ? S.ca[i] * gca[i] + S.cb[i] * gcb[i] + 2.0 * m * S.ca[i] * gcbv : 0.0;
+            if (!clamped) for (int j = 0; j < 3; ++j) c0 -= Gb[i][j] * S.H[i][j];
+        }
+        pub[15] = c0;
+    }
+    __syncthreads();
+    double Gb[3][3], pa[3], pb[3];
+    for (int i = 0; i < 3; ++i) {
+        pa[i] = pub[9 + i];
+        pb[i] = pub[12 + i];
+        for (int j = 0; j < 3; ++j) Gb[i][j] = pub[i * 3 + j];
+    }
+    const double c0 = pub[15];
+    for (int i = t; i < N; i += 256) {
+        const double wn = X.w(i) / S.norm;
+        double da[3], db[3], ga[3], gb[3];
+        for (int c = 0; c < 3; ++c) { da[c] = X.a(i, c) - S.ca[c]; db[c] = X.b(i, c) - S.cb[c]; }
+        double gw = c0;
+        for (int r = 0; r < 3; ++r) {
+            const double gdb = Gb[r][0] * db[0] + Gb[r][1] * db[1] + Gb[r][2] * db[2];
+            const double gtda = Gb[0][r] * da[0] + Gb[1][r] * da[1] + Gb[2][r] * da[2];
+            ga[r] = wn * (gdb + pa[r]);
+            gb[r] = wn * (gtda + pb[r]);
+            gw += da[r] * (gdb + pa[r]) + db[r] * pb[r];
+        }
+        Y.put(i, ga, gb, gw / S.norm);
+    }
+}
+__global__ __launch_bounds__(256) void kabsch_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ w,
+                                                         const float* __restrict__ g, float* ga, float* gb, float* gw, int N, float eps)
+{
+    const size_t p = blockIdx.x;
+    KabschDense X{a + p * N * 3, b + p * N * 3, w + p * N};
+    KabschDenseGrad Y{ga ? ga + p * N * 3 : nullptr, gb ? gb + p * N * 3 : nullptr, gw ? gw + p * N : nullptr};
+    kabsch_bwd_body(X, N, g + p * 12, eps, Y);
+}
+// blocks [0, P*L): one per (pair, layer) problem, as the forward.  Blocks [P*L, P*L + ceil(R/256)): the rows of [L,R] no problem covers get zeros (each
+// row is written by exactly one block: no atomics, no ordering against a memset).
+__global__ __launch_bounds__(256) void kabsch_pairs_bwd_kernel(const float* __restrict__ xyz, const float* __restrict__ corr, const float* __restrict__ ov,
+                                                               const int* __restrict__ probs, const float* __restrict__ g, float* gcorr, float* gov,
+                                                               int P, int L, int R, float eps)
+{
+    if ((int)blockIdx.x >= P * L) {
+        const int r = ((int)blockIdx.x - P * L) * 256 + (int)threadIdx.x;
+        if (r >= R) return;
+        for (int p = 0; p < P; ++p) {
+            const int* pr = probs + p * 4;
+            if ((r >= pr[0] && r < pr[0] + pr[1]) || (r >= pr[2] && r < pr[2] + pr[3])) return;
+        }
+        for (int l = 0; l < L; ++l) {
+            if (gcorr) for (int c = 0; c < 3; ++c) gcorr[((size_t)l * R + r) * 3 + c] = 0.f;
+            if (gov) gov[(size_t)l * R + r] = 0.f;
+        }
+        return;
+    }
+    const int p = blockIdx.x / L, l = blockIdx.x % L;
+    const int* pr = probs + p * 4;
+    KabschPair X{xyz, corr + (size_t)l * R * 3, ov + (size_t)l * R, pr[0], pr[1], pr[2]};
+    KabschPairGrad Y{gcorr ? gcorr + (size_t)l * R * 3 : nullptr, gov ? gov + (size_t)l * R : nullptr, pr[0], pr[1], pr[2]};
+    kabsch_bwd_body(X, pr[1] + pr[3], g + (size_t)blockIdx.x * 12, eps, Y);
 }
 
 // ------------------------------------------------------------------------------------------------ voxel-average downsample
@@ -840,6 +994,29 @@ int dreg_weighted_kabsch_pairs(const float* xyz, const float* corr, const float*
 {
     if (P == 0 || L == 0) return DREG_OK;
     hipLaunchKernelGGL(kabsch_pairs_kernel, dim3(P * L), dim3(256), 0, (hipStream_t)stream, xyz, corr, ov, probs, out, L, R, eps);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+// Backward of dreg_weighted_kabsch: g_out [P,3,4] -> g_a, g_b [P,N,3], g_w [P,N] (each may be null: skipped).  Deterministic, no atomics.
+int dreg_weighted_kabsch_bwd(const float* a, const float* b, const float* w, const float* g_out, float* g_a, float* g_b, float* g_w, int P, int N,
+                             float eps, void* stream)
+{
+    if (P < 0 || N < 0) return DREG_EINVAL;
+    if (P == 0) return DREG_OK;
+    hipLaunchKernelGGL(kabsch_bwd_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, a, b, w, g_out, g_a, g_b, g_w, N, eps);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+// Backward of dreg_weighted_kabsch_pairs: g_out [P,L,3,4] -> g_corr [L,R,3], g_ov [L,R] (each may be null), every row written (rows of no problem: 0).
+int dreg_weighted_kabsch_pairs_bwd(const float* xyz, const float* corr, const float* ov, const int* probs, const float* g_out, float* g_corr, float* g_ov,
+                                   int P, int L, int R, float eps, void* stream)
+{
+    if (P < 0 || L < 0 || R < 0) return DREG_EINVAL;
+    if (L == 0 || R == 0 || (g_corr == nullptr && g_ov == nullptr)) return DREG_OK;
+    const int nz = (R + 255) / 256;
+    hipLaunchKernelGGL(kabsch_pairs_bwd_kernel, dim3(P * L + nz), dim3(256), 0, (hipStream_t)stream, xyz, corr, ov, probs, g_out, g_corr, g_ov, P, L, R, eps);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
 }

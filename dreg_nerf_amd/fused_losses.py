@@ -151,3 +151,47 @@ def regtr_losses(batched: dict, poses, feature_loss, gt, tilde, robust: bool = F
     out = {k: stats[i] for i, k in enumerate(NAMES[:4])}
     out["total"] = total
     return out
+
+
+def _source_rows(tab, dev):
+    """(row, pair) int64 [2, N_src] and 1/ns [N_src] of every pair's source key points in the shared row space (cached on the table: one upload)."""
+    hit = getattr(tab, "_pose_rows", None)
+    if hit is None:
+        import numpy as np
+        rows = np.concatenate([np.arange(s0, s0 + ns) for (s0, ns, _, _) in tab.segs])
+        pair = np.concatenate([np.full(ns, p) for p, (_, ns, _, _) in enumerate(tab.segs)])
+        inv = np.concatenate([np.full(ns, 1.0 / ns, dtype=np.float32) for (_, ns, _, _) in tab.segs])
+        meta = torch.from_numpy(np.stack([rows, pair]).astype(np.int64))
+        inv = torch.from_numpy(inv)
+        if dev.type == "cuda":
+            meta, inv = meta.pin_memory().to(dev, non_blocking=True), inv.pin_memory().to(dev, non_blocking=True)
+        hit = tab._pose_rows = (meta, inv)
+    return hit
+
+
+def pose_loss(batched: dict, poses_gt, layers: str = "last", eps: float = 1e-6):
+    """Opt-in pose supervision: the reference's correspondence metric (conerf/loss/correspondence_loss.py, 'mae', unweighted) on the source key points
+    moved by the PREDICTED pose instead of the predicted correspondences, mean_i sum_c |T^ x_i - T_gt x_i|_c, averaged over the pairs and the chosen
+    decoder layers.  The pose comes from the differentiable Kabsch solve (attn_ops.weighted_kabsch_pairs_grad) of every pair at once.
+    layers = "last": from the last layer's own tensors (corr_last / ov_last of the point-set executor: its backward keeps the last-only path; the per-op
+    path's corr[-1] / ov[-1] otherwise), as every loss of the reference reads the last layer.  "all": the six layers.  poses_gt [P,4,4]."""
+    from . import attn_ops as A
+    if layers == "last":
+        corr = batched["corr_last"] if "corr_last" in batched else batched["corr"][-1]
+        ov = batched["ov_last"] if "ov_last" in batched else batched["ov"][-1]
+        corr, ov = corr[None], ov[None]
+    elif layers == "all":
+        corr, ov = batched["corr"], batched["ov"]
+    else:
+        raise ValueError(f"pose_loss: layers must be 'last' or 'all' (got {layers!r})")
+    xyz, tab = batched["xyz"], batched["tab"]
+    T = A.weighted_kabsch_pairs_grad(xyz, corr, ov, tab, eps)                   # [P, L, 3, 4]
+    meta, inv = _source_rows(tab, xyz.device)
+    rows, pair = meta[0], meta[1]
+    x = xyz.detach()[rows]                                                      # [N_src, 3]
+    Tp = T[pair]                                                                # [N_src, L, 3, 4]
+    Tg = poses_gt.float()[pair]                                                 # [N_src, 4, 4]
+    moved = (Tp[..., :3] @ x[:, None, :, None])[..., 0] + Tp[..., 3]            # [N_src, L, 3]
+    target = (Tg[:, :3, :3] @ x[..., None])[..., 0] + Tg[:, :3, 3]              # [N_src, 3]
+    err = (moved - target[:, None]).abs().sum(-1)                               # [N_src, L]
+    return (err.sum(1) * inv).sum() / (len(tab.segs) * corr.shape[0])

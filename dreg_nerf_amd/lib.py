@@ -192,6 +192,8 @@ SIGNATURES = {
     "dreg_relu_bwd": (I, [P, P, P, Z, I, I, I, P]),
     "dreg_weighted_kabsch": (I, [P, P, P, P, I, I, F, P]),
     "dreg_weighted_kabsch_pairs": (I, [P, P, P, P, P, I, I, I, F, P]),
+    "dreg_weighted_kabsch_bwd": (I, [P] * 7 + [I, I, F, P]),
+    "dreg_weighted_kabsch_pairs_bwd": (I, [P] * 7 + [I, I, I, F, P]),
     # losses.hip
     "dreg_reg_point_losses": (I, [P] * 10 + [I, I, I, I, F, F, F, P]),
     "dreg_infonce_nn": (I, [P] * 7 + [I, I, F, P]),

@@ -94,7 +94,7 @@ def _reset_parameters(model: nn.Module, spec):
 
 class NeRFRegTr(nn.Module):
     def __init__(self, pos_emb_type: str = "sine", pos_emb_dim: int = 256, pos_emb_scaling: float = 1.0,
-                 num_downsample: int = 6, precision: str = "bf16"):
+                 num_downsample: int = 6, precision: str = "bf16", differentiable_pose: bool = False):
         super().__init__()
         if pos_emb_dim != 256:
             raise NotImplementedError("the attention / LayerNorm kernels are built for the reference's model width 256")
@@ -130,6 +130,10 @@ class NeRFRegTr(nn.Module):
         # transformer_ops.plan_hierarchical_subsample_all: pairs that have stopped subsampling pass through the later rounds unchanged)
         self.global_subsample = True
         self.fused_gather_subsample = True   # ... together with the trilinear gather in front of them (attn_ops.gather_subsample)
+        # `pose` inside autograd, as the reference's compute_rigid_transform (se3.py:89-140): in grad mode the Kabsch solve gets its backward
+        # (attn_ops.weighted_kabsch_pairs_grad) and a loss on pred['pose'] reaches the correspondences / overlap scores of all six decoder layers.
+        # False (default): the pose is returned detached (no reference loss reads it) — the same launches as without the switch.
+        self.differentiable_pose = differentiable_pose
         self._spec = params.regtr_spec(self.pos_emb_type)
         _build_tree(self, self._spec)
         _reset_parameters(self, self._spec)
@@ -493,10 +497,15 @@ class NeRFRegTr(nn.Module):
         else:
             cond, corr, ov = T.encode_decode_batched(P, feats_all, xyz_all, tab, self.position_embedding)
         outs = []
-        # `pose` is returned DETACHED (requires_grad False), on purpose: the reference's compute_rigid_transform (se3.py:89-140) sits inside autograd, but none of
-        # its training losses reads `pose` (train_nerf_regtr.py:186-229 use the correspondences, overlap scores and features), so the weighted Kabsch solve has
-        # a forward kernel only.  A pose loss added by a user gets NO gradient through `pose` (tests/test_hip_regtr.py asserts the flag).
-        poses = A.weighted_kabsch_pairs(xyz_all, corr, ov, tab)   # [P,6,3,4]: every (pair, layer) solve in one launch
+        # `pose` is returned DETACHED (requires_grad False) unless `differentiable_pose`: the reference's compute_rigid_transform (se3.py:89-140) sits inside
+        # autograd, but none of its training losses reads `pose` (train_nerf_regtr.py:186-229 use the correspondences, overlap scores and features), so by
+        # default the solve runs without a backward (tests/test_hip_regtr.py asserts the flag).  With differentiable_pose in grad mode the same launch runs
+        # inside an autograd node whose backward (one launch: csrc/pointset.hip kabsch_pairs_bwd_kernel) carries a pose loss into corr / ov of all six
+        # layers — through the point-set executor's full (not last-only) backward.
+        if self.differentiable_pose and torch.is_grad_enabled():
+            poses = A.weighted_kabsch_pairs_grad(xyz_all, corr, ov, tab)   # [P,6,3,4]
+        else:
+            poses = A.weighted_kabsch_pairs(xyz_all, corr, ov, tab)   # [P,6,3,4]: every (pair, layer) solve in one launch
         if not self.training and self.__dict__.get("_stem_violation") is not None:
             # evaluation: a call that was handed a grid with values outside its voxel_mask must not return a plausible pose — the poses of THIS call become
             # NaN on the device (no host sync here); check_inputs() / the next call raise with the explanation

@@ -172,8 +172,14 @@ class _SplitLabels:
 class TrainStep:
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-4, grad_clip: float = 0.1,
                  robust_loss: bool = False, step_lr: int = 34000, gamma: float = 0.5, finetune: bool = False,
-                 label_fn: Optional[Callable] = None, fused_losses: bool = True):
+                 label_fn: Optional[Callable] = None, fused_losses: bool = True, pose_loss_weight: float = 0.0, pose_loss_layers: str = "last"):
         self.model = model
+        # Opt-in pose supervision (not in the reference's step): 'total' += pose_loss_weight * fused_losses.pose_loss over the last decoder layer
+        # ("last") or all six ("all"), from the differentiable Kabsch solve of last_batched — independent of model.differentiable_pose.  0: the step is unchanged.
+        if pose_loss_layers not in ("last", "all"):
+            raise ValueError(f"pose_loss_layers must be 'last' or 'all' (got {pose_loss_layers!r})")
+        self.pose_loss_weight = float(pose_loss_weight)
+        self.pose_loss_layers = pose_loss_layers
         dev = next(model.parameters()).device
         self.feature_loss = LS.InfoNCELoss(256, 0.2, 0.4).to(dev)
         self.params = [p for p in model.parameters()]
@@ -271,6 +277,11 @@ class TrainStep:
                 for k, v in ls.items():
                     agg[k] = agg.get(k, 0.0) + v.detach()
             total = total / len(batch)
+        pose_l = None
+        if self.pose_loss_weight > 0:
+            poses_gt = torch.cat([d["pose"].reshape(1, 4, 4) for d in batch]).float().to(dev0)
+            pose_l = FL.pose_loss(self.model.last_batched, poses_gt, self.pose_loss_layers)
+            total = total + self.pose_loss_weight * pose_l
         dev = next(self.model.parameters()).device
         sync = None
         if self.world > 1 or self.force_grad_sync:
@@ -313,6 +324,9 @@ class TrainStep:
         if lab is not None:
             lab.join()                     # readers of the loss values (this stream) come behind the label stream's completion of 'nerf_cont' / 'total'
         self.last_losses = means if agg is None else {k: v / len(batch) for k, v in agg.items()}
+        if pose_l is not None:             # (after lab.join(): 'total' of the split-label path is complete on this stream only from here)
+            self.last_losses["pose"] = pose_l.detach()
+            self.last_losses["total"] = self.last_losses["total"] + self.pose_loss_weight * pose_l.detach()
         self.last_preds = preds
         from . import visibility
         # labels marched from NeRF blocks: a persistent launch that ran into its pass bound (points left unlabelled) is reported here as soon as its

@@ -525,6 +525,14 @@ int dreg_weighted_kabsch(const float* a, const float* b, const float* w, float* 
  * xyz [R,3], corr [L,R,3], ov [L,R], probs int32 [P][4] = (s0, ns, t0, nt) -> out [P,L,3,4] */
 int dreg_weighted_kabsch_pairs(const float* xyz, const float* corr, const float* ov, const int* probs, float* out, int P, int L,
                                int R, float eps, void* stream);
+/* backward of dreg_weighted_kabsch: g_out fp32 [P,3,4] = dLoss/dout -> g_a, g_b [P,N,3], g_w [P,N] (each may be null: not computed).
+ * Closed form in fp64 on the forward's own SVD; finite for finite inputs (rotations the data does not determine get no gradient); no atomics. */
+int dreg_weighted_kabsch_bwd(const float* a, const float* b, const float* w, const float* g_out, float* g_a, float* g_b, float* g_w, int P, int N,
+                             float eps, void* stream);
+/* backward of dreg_weighted_kabsch_pairs: g_out [P,L,3,4] -> g_corr [L,R,3], g_ov [L,R] (each may be null).  Source rows take the gradient of b,
+ * target rows that of a, ov that of w; rows no problem covers are written as zeros; xyz gets none (data). */
+int dreg_weighted_kabsch_pairs_bwd(const float* xyz, const float* corr, const float* ov, const int* probs, const float* g_out, float* g_corr,
+                                   float* g_ov, int P, int L, int R, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- training losses
  * train_nerf_regtr.py:186-229 for all P pairs of a step (rows = every pair's (src | tgt) key points, probs as above):

@@ -77,7 +77,8 @@ def main():
     if world > 1:
         for p in model.parameters():
             dist.broadcast(p.data, 0)
-    ts = TrainStep(model, lr=cfg.lr, robust_loss=cfg.robust_loss, finetune=cfg.finetune)
+    ts = TrainStep(model, lr=cfg.lr, robust_loss=cfg.robust_loss, finetune=cfg.finetune, pose_loss_weight=cfg.pose_loss_weight,
+                   pose_loss_layers=cfg.pose_loss_layers)
     save_dir = os.path.join(cfg.root_dir, "out", cfg.expname)
     ckpt = CheckPointManager(save_dir if rank == 0 else None, verbose=rank == 0)
     if rank == 0:
