@@ -45,6 +45,8 @@ def config_parser(argv=None):
     p.add_argument("--synthetic_res", type=int, default=128)
     p.add_argument("--dump_outputs", action="store_true",
                    help="eval: per scene, transformation_est.json and the registration's point clouds as PLY files (eval_nerf_regtr.py:313-438)")
+    p.add_argument("--render_views", action="store_true",
+                   help="eval: per scene, render both NeRF blocks under the ground-truth, predicted and no alignment (render_videos, eval_nerf_regtr.py:113-172,345-369)")
     p.add_argument("--fgr_baseline", action="store_true",
                    help="also run the Fast Global Registration baseline on every pair and write fgr_metrics_{split}.json (eval_nerf_regtr.py:303-311 of the reference)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")

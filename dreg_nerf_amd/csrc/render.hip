@@ -1,0 +1,304 @@
+// Volume rendering of one NeRF block (Instant-NGP field + occupancy grid), gfx950: the reference's render_image
+// (conerf/utils/utils.py:44-141) = nerfacc 0.3.5 ray_marching(sigma_fn, early_stop_eps = 1e-4, alpha_thre, stratified = False) followed by
+// rendering(rgb_sigma_fn, render_bkgd), in ONE persistent kernel that keeps no sample list.  nerfacc is absent from the reference tree: parity
+// is unpinned, the rule below is the specification (DESIGN.md "Volume renderer"; CPU restatement: tests/render_restatement.py).
+//
+// For a ray with origin o and unit direction d (the reference marches along viewdirs):
+//   t_min, t_max   slab test against the scene aabb (t_min clamped at 0), then t_min = max(t_min, near), t_max = min(t_max, far);
+//                  a ray that misses the aabb has no samples
+//   samples        t_mid = t_min + (n + 1/2) dt while t_mid < t_max, kept only where the occupancy cell (over the roi aabb, floor + clamp;
+//                  outside the roi = unoccupied) is set
+//   alpha          1 - exp(-sigma(o + t_mid d) dt)
+//   T_all          exclusive product of (1 - alpha) over ALL marched samples; a sample SURVIVES iff T_all >= early_stop_eps and
+//                  (alpha_thre == 0 or alpha >= alpha_thre); the ray ends once T_all < early_stop_eps
+//   weights        over the survivors only: w_k = alpha_k prod_{j<k, j survives} (1 - alpha_j)   (rendering() of the pruned list)
+//   outputs        rgb = sum w c + bkgd (1 - sum w), opacity = sum w, depth = sum w t_mid (not normalised), n_samples = survivors
+//
+// One lane = one ray.  A lane whose ray has ended takes the next one from a queue (one atomic per wave and refill, as vis_march_queue).  Per
+// pass every live lane advances to its next occupied lattice sample (march.h), the wave evaluates the 64 densities together on fp16 MFMA,
+// each lane composites its own sample in ray order, and the colour net (SH4(d) | 15 features | 1 -> 64 -> 64 -> 3, sigmoid: the arithmetic of
+// ngp_rgb_kernel with per-point directions) runs only when some lane's sample survived — the rows of surviving lanes are the live ones.
+// SH4(d) is formed once per ray.  A ray's result depends on nothing but its own samples: output is bit-identical between runs and launch widths.
+#include "march.h"
+#include "../../include/dreg_nerf.h"   // signature check of the entry point defined here
+
+struct RenderArgs {
+    const float* origins;       // [N,3]
+    const float* dirs;          // [N,3] unit viewing directions
+    long n_rays;
+    const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
+    const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]
+    NgpLevelsV lv;
+    const uint8_t* binary;
+    const uint32_t* coarse;     // optional coarse bits (dreg_occupancy_coarse_bits), <= 32,768 bits; null = none
+    int rx, ry, rz, cx, cy, cz;
+    float roi[6], scene[6], model[6];
+    float near, far, dt, alpha_thre, eps;
+    float bkgd[3];
+    int n_max;                  // samples per ray <= ceil(aabb diagonal / dt) + 1 (every ray's ceil((t_max - t_min) / dt) + 1 is below it)
+    long pass_bound;            // passes of the march loop per wave: n_rays * (n_max + 2) + 64 (a safety net: every pass takes a ray or a step)
+    float *rgb, *opacity, *depth;
+    unsigned long long* n_samples;
+    unsigned long long* queue;
+};
+
+DREG_KNOB(int, g_render_waves, 2048);     // tuning (include/dreg_nerf_probe.h): one-wave workgroups of the launch (256 CUs x 8: 19.7 KB of LDS each)
+
+__device__ __forceinline__ void render_write(const RenderArgs& a, long ray, const float (&acc)[3], float opac, float dep)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.rgb[ray * 3 + k] = acc[k] + a.bkgd[k] * (1.f - opac);
+    a.opacity[ray] = opac;
+    a.depth[ray] = dep;
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ngp_render_kernel(RenderArgs a)
+{
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+    __shared__ __attribute__((aligned(16))) char sX[64 * MARCH_XRS];
+    __shared__ __attribute__((aligned(16))) char sH[64 * MARCH_HRS];
+    __shared__ float sOut[64];
+    __shared__ __attribute__((aligned(16))) float sO[64 * 4];
+    __shared__ uint32_t sCoarse[1024];
+    const int lane = threadIdx.x;
+    const int fr = lane & 15, kg = lane >> 4;
+    const bool use_coarse = a.coarse != nullptr;
+    if (use_coarse) {
+        const int nw = (a.cx * a.cy * a.cz + 31) / 32;
+        for (int i = lane; i < nw; i += 64) sCoarse[i] = a.coarse[i];
+    }
+    __syncthreads();
+    MarchGrid g;
+    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
+    g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
+    MarchDensityW dw;
+    march_load_density_w(dw, a.w1, a.w2, lane);
+    f16x8_t cw1f[4], cw3f[2];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(a.cw3 + fr * 64 + kb * 32 + kg * 8);
+
+    // per-lane ray state
+    bool active = false, exhausted = false;
+    long ray = 0;
+    int n = 0, n_lim = 0;
+    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f}, tmin = 0.f, tmax = 0.f;
+    float T_all = 1.f, T_s = 1.f, acc[3] = {0.f, 0.f, 0.f}, opac = 0.f, dep = 0.f;
+    uint32_t sh2[8];            // fp16 SH4(d), two per word
+    unsigned long long my_samples = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sh2[j] = 0u;
+
+    bool finished = false;
+    for (long it = 0; it < a.pass_bound; ++it) {
+        // ---- refill: lanes without a ray take the next ones from the queue; rays that miss the aabb are written at once
+        for (int tries = 0; tries < 1024; ++tries) {
+            const bool need = !active && !exhausted;
+            const unsigned long long mask = __ballot(need);
+            if (!mask) break;
+            unsigned long long base = 0;
+            const int leader = __ffsll((long long)mask) - 1;
+            if (lane == leader) base = atomicAdd(a.queue, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader, 64);
+            if (need) {
+                const unsigned long long r = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+                if (r >= (unsigned long long)a.n_rays) exhausted = true;
+                else {
+                    ray = (long)r;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { o[k] = a.origins[ray * 3 + k]; d[k] = a.dirs[ray * 3 + k]; }
+                    float near = -1e30f, far = 1e30f;
+                    bool hit = true;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        if (d[k] == 0.f) { hit = hit && o[k] >= a.scene[k] && o[k] <= a.scene[3 + k]; continue; }   // parallel to the slab
+                        const float id = 1.f / d[k];
+                        float t0 = (a.scene[k] - o[k]) * id, t1 = (a.scene[3 + k] - o[k]) * id;
+                        if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
+                        near = fmaxf(near, t0); far = fminf(far, t1);
+                    }
+                    hit = hit && near <= far && far > 0.f;
+                    tmin = fmaxf(fmaxf(near, 0.f), a.near);
+                    tmax = fminf(far, a.far);
+                    const float acc0[3] = {0.f, 0.f, 0.f};
+                    if (!hit || !(tmin < tmax)) render_write(a, ray, acc0, 0.f, 0.f);
+                    else {
+                        active = true; n = 0; T_all = 1.f; T_s = 1.f; opac = 0.f; dep = 0.f;
+                        acc[0] = acc[1] = acc[2] = 0.f;
+                        n_lim = (int)fminf(ceilf((tmax - tmin) / a.dt) + 1.f, (float)a.n_max);      // (a.n_max <= 1e8 + 2: the conversion cannot overflow)
+                        const float x = d[0], y = d[1], z = d[2];
+                        const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+                        const float sh[16] = {0.28209479177387814f, -0.48860251190291987f * y, 0.48860251190291987f * z, -0.48860251190291987f * x,
+                                              1.0925484305920792f * xy, -1.0925484305920792f * yz, 0.94617469575755997f * z2 - 0.31539156525251999f,
+                                              -1.0925484305920792f * xz, 0.54627421529603959f * x2 - 0.54627421529603959f * y2,
+                                              0.59004358992664352f * y * (-3.0f * x2 + y2), 2.8906114426405538f * xy * z,
+                                              0.45704579946446572f * y * (1.0f - 5.0f * z2), 0.3731763325901154f * z * (5.0f * z2 - 3.0f),
+                                              0.45704579946446572f * x * (1.0f - 5.0f * z2), 1.4453057213202769f * z * (x2 - y2),
+                                              0.59004358992664352f * x * (-x2 + 3.0f * y2)};
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const f16x2_t p = {(_Float16)sh[2 * j], (_Float16)sh[2 * j + 1]};
+                            sh2[j] = __builtin_bit_cast(uint32_t, p);
+                        }
+                    }
+                }
+            }
+        }
+        if (!__any(active)) {
+            if (__all(exhausted)) { finished = true; break; }        // the queue is empty and nothing is in flight
+            continue;                                                // (a long run of missed rays used up this pass's refill rounds)
+        }
+        // ---- advance every live ray to its next lattice sample inside an occupied cell
+        float x[3] = {0.f, 0.f, 0.f}, tm = 0.f;
+        const bool was_active = active;
+        if (active && n >= n_lim) active = false;                   // (never taken: t_mid >= t_max ends a ray first; the argument-derived bound per ray)
+        const bool have = march_advance(g, o, d, tmin, tmax, a.dt, n, active, x, &tm, 4096);
+        if (was_active && !active) render_write(a, ray, acc, opac, dep);       // left [t_min, t_max)
+        if (!__any(have)) continue;
+        // ---- density of the wave's samples; their features land in the colour net's input rows
+        const bool inside_m = march_density<true>(have, x, a.model, a.lv, a.table, dw, sX, sH, sOut, lane);
+        bool surv = false;
+        float w = 0.f;
+        if (have) {
+            const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
+            const float alpha = 1.f - __expf(-sigma * a.dt);
+            surv = T_all >= a.eps && (a.alpha_thre <= 0.f || alpha >= a.alpha_thre);
+            T_all *= (1.f - alpha);
+            ++n;
+            if (surv) {
+                w = alpha * T_s;
+                T_s *= (1.f - alpha);
+                uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * MARCH_XRS);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
+                reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS)[31] = (_Float16)1.f;
+            }
+        }
+        if (__any(surv)) {
+            // ---- colour of the surviving samples: X = (fp16 SH4(d) | 15 features | 1) -> relu 64 -> relu 64 -> 3, sigmoid (as ngp_rgb_kernel)
+            march_wave_sync();
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) {
+                const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * MARCH_XRS + kg * 16);
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    const f32x4_t v = __builtin_amdgcn_mfma_f32_16x16x32_f16(cw1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
+                    f16x2_t p = {(_Float16)v[0], (_Float16)v[1]}, q = {(_Float16)v[2], (_Float16)v[3]};
+                    p = __builtin_elementwise_max(p, z);
+                    q = __builtin_elementwise_max(q, z);
+                    uint32_t* dst = reinterpret_cast<uint32_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+                    dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
+                }
+            }
+            march_wave_sync();
+            // second layer in place: a 16-row block is read into registers in full before its outputs are written
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) {
+                f16x8_t af[2];
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) af[kb] = *reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2);
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    f32x4_t h = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb)
+                        h = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(a.cw2 + (cb * 16 + fr) * 64 + kb * 32 + kg * 8), af[kb], h, 0, 0, 0);
+                    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
+                    f16x2_t p = {(_Float16)h[0], (_Float16)h[1]}, q = {(_Float16)h[2], (_Float16)h[3]};
+                    p = __builtin_elementwise_max(p, z);
+                    q = __builtin_elementwise_max(q, z);
+                    uint32_t* dst = reinterpret_cast<uint32_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+                    dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
+                }
+            }
+            march_wave_sync();
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) {
+                f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+                    ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2), cw3f[kb], ov, 0, 0, 0);
+                if (fr < 4) {        // channel fr of samples rb*16 + kg*4 + r (channel 3 is padding: written, never read)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sO[(rb * 16 + kg * 4 + r) * 4 + fr] = ov[r];
+                }
+            }
+            march_wave_sync();
+            if (surv) {
+                const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
+                const float pv[3] = {pre.x, pre.y, pre.z};
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float hv = (float)(_Float16)pv[ch];
+                    const float c = (float)(_Float16)__builtin_amdgcn_rcpf(1.f + __expf(-hv));
+                    acc[ch] += w * c;
+                }
+                opac += w;
+                dep += w * tm;
+                ++my_samples;
+            }
+        }
+        if (have && T_all < a.eps) { active = false; render_write(a, ray, acc, opac, dep); }    // transmittance below early_stop_eps: the ray ends
+        march_wave_sync();
+    }
+    // the survivors this wave composited: one atomic per wave
+    unsigned long long tot = my_samples;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+    if (lane == 0 && tot) atomicAdd(a.n_samples, tot);
+    // the bound was reached with rays still queued or in flight: say so in bit 63 of the ray counter (dreg_nerf_amd/render.py raises)
+    if (!finished && lane == 0) atomicOr(a.queue, 1ull << 63);
+}
+
+extern "C" {
+
+// Render n_rays rays of one block.  Caller-owned device buffers: origins / viewdirs fp32 [N,3], binary uint8 [rx,ry,rz], coarse_bits (optional),
+// the fp16 inference copies (table / w1 / w2 of mlp_base.params, cw1 / cw2 / cw3 of color_mlp.params), rgb fp32 [N,3], opacity / depth fp32 [N],
+// n_samples: one u64 and queue: 8 bytes, both zeroed by the caller on `stream`.  Level arrays, aabbs and bkgd are HOST pointers.
+int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, const uint8_t* binary, int rx, int ry, int rz, const uint32_t* coarse_bits,
+                    const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                    const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                    const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                    float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                    float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
+{
+    if (n_rays < 0 || rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
+    if (n_rays == 0) return DREG_OK;
+    if (!origins || !viewdirs || !binary || !table || !w1 || !w2 || !cw1 || !cw2 || !cw3 || !offset || !size || !res || !scale || !hashed ||
+        !roi_aabb || !scene_aabb || !model_aabb || !bkgd || !rgb || !opacity || !depth || !n_samples || !queue)
+        return DREG_EINVAL;
+    RenderArgs a;
+    a.origins = origins; a.dirs = viewdirs; a.n_rays = n_rays;
+    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
+    a.cw1 = (const _Float16*)cw1; a.cw2 = (const _Float16*)cw2; a.cw3 = (const _Float16*)cw3;
+    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
+    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
+    for (int k = 0; k < 3; ++k) a.bkgd[k] = bkgd[k];
+    a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;
+    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
+    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;      // (the kernel keeps the bits in 4 KB of LDS)
+    a.near = near_plane; a.far = far_plane; a.dt = render_step_size; a.alpha_thre = alpha_thre; a.eps = early_stop_eps;
+    double diag = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = (double)scene_aabb[3 + k] - (double)scene_aabb[k]; diag += e * e; }
+    diag = __builtin_sqrt(diag);
+    if (!(diag >= 0.0) || diag / render_step_size > 1e8) return DREG_EINVAL;        // (a degenerate aabb or a step too small to march)
+    a.n_max = (int)__builtin_ceil(diag / render_step_size) + 2;
+    const double passes = (double)n_rays * (double)(a.n_max + 2) + 64.0;
+    a.pass_bound = passes > 1e15 ? (long)1e15 : (long)passes;
+    a.rgb = rgb; a.opacity = opacity; a.depth = depth; a.n_samples = n_samples; a.queue = (unsigned long long*)queue;
+    long waves = (n_rays + 63) / 64;
+    if (waves > g_render_waves) waves = g_render_waves;
+    hipLaunchKernelGGL(ngp_render_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+#ifdef DREG_PROBE
+void dreg_render_set_waves(int n) { g_render_waves = n > 0 ? n : 2048; }
+#endif
+
+}  // extern "C"

@@ -11,16 +11,8 @@
 // needed, so a ray stops as soon as the label is decided: hit (max >= cut_off), or T < max(cut_off, early_stop_eps)
 // (alpha*T <= T can no longer reach cut_off) — no sample list, no later samples evaluated.  Labels of a point are OR-ed
 // over cameras with one atomic per hit.  nerfacc 0.3.5 / tcnn are absent from the reference tree: parity unpinned.
-#include "common.h"
+#include "march.h"      // NgpLevelsV, vgrid_index, the lattice advance and the density MLP shared with render.hip
 #include <cstring>
-
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-struct NgpLevelsV {
-    uint32_t offset[16], size[16], res[16];
-    float scale[16];
-    uint32_t hashed[16];
-};
 struct VisArgs {
     const float* cams;     // [Nc,3] camera centres
     const float* pts;      // [Np,3]
@@ -36,11 +28,6 @@ struct VisArgs {
     int cx, cy, cz;           // its extents: ceil(r / 4)
     unsigned long long* queue;   // persistent forms: this block's ray counter (zeroed by the caller)
 };
-
-__device__ __forceinline__ uint32_t vgrid_index(uint32_t x, uint32_t y, uint32_t z, uint32_t res, uint32_t size, uint32_t hashed) {
-    uint32_t idx = hashed ? (x ^ (y * 2654435761u) ^ (z * 805459861u)) : (x + y * res + z * res * res);
-    return idx % size;
-}
 
 __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
 {
@@ -208,8 +195,7 @@ static constexpr long g_pass_bound = 1L << 22;
 __device__ __forceinline__ void vwave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long long* __restrict__ queue)
 {
-    constexpr int XRS = 32 * 2 + 16, HRS = 64 * 2 + 16;
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+    constexpr int XRS = MARCH_XRS, HRS = MARCH_HRS;
     __shared__ __attribute__((aligned(16))) char smem[64 * XRS + 64 * HRS + 64 * 4];
     char* sX = smem;
     char* sH = sX + 64 * XRS;
@@ -226,15 +212,14 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
     }
     __syncthreads();
     const unsigned long long nrays = (unsigned long long)a.Nc * (unsigned long long)a.Np;
-    const float roi_ext[3] = {a.roi[3] - a.roi[0], a.roi[4] - a.roi[1], a.roi[5] - a.roi[2]};
-    const int rdim[3] = {a.rx, a.ry, a.rz};
+    MarchGrid g;
+    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
+    g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
     const float stop_T = fmaxf(a.cut_off, a.early_eps);
-    const int fr = lane & 15, kg = lane >> 4;
-    f16x8_t w1f[4], w2f[2];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) w1f[cb] = *reinterpret_cast<const f16x8_t*>(a.w1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) w2f[kb] = *reinterpret_cast<const f16x8_t*>(a.w2 + fr * 64 + kb * 32 + kg * 8);
+    MarchDensityW dw;
+    march_load_density_w(dw, a.w1, a.w2, lane);
 
     // per-lane ray state
     bool active = false, exhausted = false;
@@ -285,108 +270,11 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
             continue;                                                // (a long run of skipped rays used up this pass's refill rounds)
         }
         // ---- advance every live ray to its next lattice sample inside an occupied cell
-        bool have = false;
         float x[3] = {0.f, 0.f, 0.f};
-        for (int guard = 0; active && !have && guard < 4096; ++guard) {
-            const float tm = tmin + ((float)n + 0.5f) * a.dt;
-            if (tm >= tmax) { active = false; break; }
-            float u[3];
-            bool inside = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { x[k] = o[k] + tm * d[k]; u[k] = (x[k] - a.roi[k]) / roi_ext[k]; inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
-            int ci[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)rdim[k]), 0), rdim[k] - 1);
-            // an empty COARSE cell holds no occupied fine cell: skip to ITS exit (the same lattice samples are visited as cell by cell:
-            // only samples inside empty fine cells are passed over, and the skip count is the same conservative floor)
-            int cell_lo[3] = {ci[0], ci[1], ci[2]}, cell_w = 1;
-            bool occ = false;
-            if (inside) {
-                bool coarse_empty = false;
-                if (use_coarse) {
-                    const int b = ((ci[0] >> 2) * a.cy + (ci[1] >> 2)) * a.cz + (ci[2] >> 2);
-                    coarse_empty = ((sCoarse[b >> 5] >> (b & 31)) & 1u) == 0u;
-                }
-                if (coarse_empty) { cell_lo[0] = ci[0] & ~3; cell_lo[1] = ci[1] & ~3; cell_lo[2] = ci[2] & ~3; cell_w = 4; }
-                else occ = a.binary[((long)ci[0] * a.ry + ci[1]) * a.rz + ci[2]] != 0;
-            }
-            if (occ) { have = true; break; }
-            float texit = 1e30f;
-            if (inside) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (d[k] != 0.f) {
-                        const int hi = min(cell_lo[k] + cell_w, rdim[k]);                // (a ragged last coarse cell ends at the grid's face)
-                        const float face = a.roi[k] + (float)(d[k] > 0.f ? hi : cell_lo[k]) * roi_ext[k] / (float)rdim[k];
-                        texit = fminf(texit, fmaxf((face - x[k]) / d[k], 0.f));
-                    }
-                }
-            } else texit = 0.f;
-            const int skip = (int)floorf(texit / a.dt - 1e-3f);
-            n += 1 + max(skip, 0);
-        }
+        const bool have = march_advance(g, o, d, tmin, tmax, a.dt, n, active, x, nullptr, 4096);
         if (!__any(have)) continue;
         // ---- density of the 64 samples
-        float u[3];
-        bool inside_m = have;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u[k] = (x[k] - a.model[k]) / (a.model[3 + k] - a.model[k]);
-            inside_m = inside_m && u[k] > 0.f && u[k] < 1.f;
-            u[k] = fminf(fmaxf(u[k], 0.f), 1.f);
-        }
-#pragma unroll 2
-        for (int l = 0; l < 16; ++l) {
-            float f0 = 0.f, f1 = 0.f;
-            if (have) {
-                const float sc = a.lv.scale[l];
-                const uint32_t res = a.lv.res[l], size = a.lv.size[l], hashed = a.lv.hashed[l];
-                const _Float16* tl = a.table + (size_t)a.lv.offset[l] * 2;
-                float w[3];
-                uint32_t g[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { const float pos = u[k] * sc + 0.5f; const float fl = floorf(pos); g[k] = (uint32_t)fl; w[k] = pos - fl; }
-#pragma unroll
-                for (int corner = 0; corner < 8; ++corner) {
-                    const uint32_t cx = g[0] + (corner & 1), cy = g[1] + ((corner >> 1) & 1), cz = g[2] + ((corner >> 2) & 1);
-                    const float wt = ((corner & 1) ? w[0] : 1.f - w[0]) * ((corner & 2) ? w[1] : 1.f - w[1]) * ((corner & 4) ? w[2] : 1.f - w[2]);
-                    union { uint32_t u32; _Float16 h[2]; } cv;
-                    cv.u32 = *reinterpret_cast<const uint32_t*>(tl + (size_t)vgrid_index(cx, cy, cz, res, size, hashed) * 2);
-                    f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
-                }
-            }
-            _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * XRS);
-            xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
-        }
-        vwave_sync();
-        f32x4_t acc[4][4];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * XRS + kg * 16);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const f32x4_t v = acc[rb][cb];       // hidden units cb*16 + kg*4 .. +3 of sample rb*16 + fr
-                const f16x4_t h = {(_Float16)fmaxf(v[0], 0.f), (_Float16)fmaxf(v[1], 0.f), (_Float16)fmaxf(v[2], 0.f), (_Float16)fmaxf(v[3], 0.f)};
-                *reinterpret_cast<f16x4_t*>(sH + (rb * 16 + fr) * HRS + (cb * 16 + kg * 4) * 2) = h;
-            }
-        vwave_sync();
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * HRS + (kb * 32 + kg * 8) * 2), w2f[kb], ov, 0, 0, 0);
-            if (fr == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sOut[rb * 16 + kg * 4 + r] = (float)(_Float16)ov[r];
-            }
-        }
-        vwave_sync();
+        const bool inside_m = march_density<false>(have, x, a.model, a.lv, a.table, dw, sX, sH, sOut, lane);
         if (have) {
             const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
             const float alpha = 1.f - __expf(-sigma * a.dt);

@@ -239,6 +239,8 @@ SIGNATURES = {
     "dreg_surface_visibility_fill_desc": (I, [P] + [P] * 7 + [P] * 5 + [P, P, P] + [I] * 5 + [F, F, F, F, P, P]),
     "dreg_surface_visibility_multi": (I, [P, I, ctypes.c_long, P]),
     "dreg_surface_visibility_multi_waves": (I, [P, I, ctypes.c_long, I, P]),
+    # render.hip
+    "dreg_ngp_render": (I, [P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
 }
 
 
@@ -276,6 +278,7 @@ PROBE_SIGNATURES = {
     "dreg_ngp_set_xcd_levels": (None, [I]),
     "dreg_visibility_set_waves": (None, [I]),
     "dreg_visibility_set_pass_bound": (I, [ctypes.c_long]),
+    "dreg_render_set_waves": (None, [I]),
 }
 PROBE_LIB_PATH = os.path.join(_HERE, "libdreg_nerf_hip_probe.so")
 _probe_lib = None

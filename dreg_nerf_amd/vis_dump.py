@@ -2,8 +2,8 @@
 JSON and the point clouds of the registration as PLY files with the reference's names and colours.  The reference writes them with
 open3d.io.write_point_cloud (absent here); the files below use the layout open3d's writer produces for a point cloud — binary
 little-endian, double x / y / z, uchar red / green / blue when coloured — so the same viewers and scripts read them.  The camera-pose
-dumps (:330-343) are written when the blocks' NeRF checkpoints (their camera_poses meta data) are on disk; the rendered videos need the
-reference's NeRF renderer and are not produced."""
+dumps (:330-343) are written when the blocks' NeRF checkpoints (their camera_poses meta data) are on disk; the renders of the two blocks
+(render_videos, :113-172) are written by eval_nerf_regtr.py --render_views (dreg_nerf_amd/render.py)."""
 import json
 import os
 

@@ -94,6 +94,7 @@ def load_block(path: str, device, cache: bool = True):
         snap = torch.load(path, map_location="cpu", weights_only=False)
     meta = {k: snap[k] for k in ("aabb", "unbounded", "grid_resolution", "contraction_type", "render_step_size", "alpha_thre",
                                  "cone_angle", "camera_poses")}
+    near_far = tuple(None if snap.get(k) is None else float(snap[k]) for k in ("near_plane", "far_plane"))
     dev = torch.device(device)
     sd, og = snap["model"], snap["occupancy_grid"]
     extra = [k for k in sd if k not in ("aabb", "mlp_base.params", "color_mlp.params") and torch.is_tensor(sd[k]) and sd[k].numel() > 0]
@@ -149,6 +150,7 @@ def load_block(path: str, device, cache: bool = True):
     kept["cam_centres_dev"] = cam_centres.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else cam_centres   # (a copy from pageable memory would stall the host on everything queued)
     kept["aabb_host"] = [float(v) for v in (meta["aabb"].tolist() if torch.is_tensor(meta["aabb"]) else meta["aabb"])]
     kept["n_occupied"], kept["grid_resolution"], kept["contraction_type"], kept["unbounded"] = n_occupied, meta["grid_resolution"], meta["contraction_type"], bool(meta["unbounded"])
+    kept["near_plane"], kept["far_plane"] = near_far          # (render.py: render_image's near / far planes; None when the block has none)
     kept["binary_u8"] = binary.contiguous().view(torch.uint8) if binary.dtype == torch.bool else binary.to(torch.uint8).contiguous()
     kept["coarse_bits"] = coarse_occupancy_bits(kept["binary_u8"])
     if not cache:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Evaluate NeRF registration on MI355X — drop-in for the metric part of the reference's eval_nerf_regtr.py
-(:224-301; with --dump_outputs also its per-scene transformation_est.json and PLY point clouds, :313-438): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+(:224-301; with --dump_outputs also its per-scene transformation_est.json and PLY point clouds, :313-438; with --render_views the renders of
+both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -71,7 +72,7 @@ def main():
     if CheckPointManager(verbose=rank == 0).load_no_config(ckpt_path, models={"model": model}, map_location=dev) == 0 and not os.path.exists(ckpt_path):
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows = {}, {}
-    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline
+    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
     # whatever the rank count — the gathered metrics file does not depend on the sharding (dreg_nerf_amd/eval_shard.py)
@@ -91,6 +92,8 @@ def main():
         if rank == 0:
             print(f"extracted {tm['blocks']} blocks ({tm['bytes_written'] / 1e9:.2f} GB of grid files) and registered {len(rows)} pairs", flush=True)
         mine = []
+        if cfg.render_views and rank == 0:
+            print("--render_views: the scenes registered by --extract_grids are not rendered (run without --extract_grids for the renders)", flush=True)
     with torch.no_grad():
         step = 1 if per_scene_extras else max(cfg.eval_batch, 1)
         for b0 in range(0, len(mine), step):
@@ -109,14 +112,21 @@ def main():
             if not per_scene_extras:
                 continue
             data, pred = batch[0], preds[0]
-            if cfg.dump_outputs:   # the reference's per-scene files (eval_nerf_regtr.py:313-321, 369-438; no videos / camera-pose dumps)
+            scene_dir = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", str(data["scene"]))
+            if cfg.dump_outputs:   # the reference's per-scene files (eval_nerf_regtr.py:313-321, 369-438; the renders are --render_views)
                 cams = [None, None]
                 sp, tp = data.get("src_nerf_path", ""), data.get("tgt_nerf_path", "")
                 if sp and tp and os.path.exists(sp) and os.path.exists(tp):       # camera_poses of the two NeRF blocks (train_ngp_nerf.py:187-209)
                     from dreg_nerf_amd.visibility import load_block
                     cams = [load_block(q, dev)[2]["camera_poses"] for q in (sp, tp)]
-                vis_dump.dump_scene_outputs(os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", str(data["scene"])), pred, data["pose"],
-                                            cams[0], cams[1])
+                vis_dump.dump_scene_outputs(scene_dir, pred, data["pose"], cams[0], cams[1])
+            if cfg.render_views:   # render_videos of the reference (eval_nerf_regtr.py:113-172, 345-369): gt / aligned / unaligned renders of both blocks
+                sp, tp = data.get("src_nerf_path", ""), data.get("tgt_nerf_path", "")
+                if sp and tp and os.path.exists(sp) and os.path.exists(tp):
+                    from dreg_nerf_amd.render import render_scene_views
+                    render_scene_views(scene_dir, sp, tp, data["pose"][0], pred["pose"][-1][0], cfg.dataset, dev)
+                else:
+                    print(f"{data['scene']}: no NeRF blocks on disk, views not rendered", flush=True)
             if cfg.fgr_baseline:   # the reference's baseline on the two voxel point clouds (global_registration.py:96-116)
                 T, sec = fgr.run_registration(_points(data, "src"), _points(data, "tgt"))
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])

@@ -716,6 +716,21 @@ int dreg_surface_visibility_multi(const void* descs_dev, int n, long total_rays,
  * (each workgroup holds 18.7 KB of LDS while the launch runs); same labels, proportionally longer */
 int dreg_surface_visibility_multi_waves(const void* descs_dev, int n, long total_rays, int max_waves, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- volume rendering of a NeRF block
+ * (csrc/render.hip) render_image of the reference (conerf/utils/utils.py:44-141: nerfacc 0.3.5 ray_marching with early_stop_eps and
+ * alpha_thre, then rendering) in one persistent kernel with no sample list; the marching and compositing rule is stated in render.hip and
+ * DESIGN.md.  origins / viewdirs fp32 [n_rays,3] (unit directions), binary uint8 [rx,ry,rz] occupancy over roi_aabb, coarse_bits optional
+ * (dreg_occupancy_coarse_bits); table / w1 / w2 = fp16 copies of mlp_base.params, cw1 / cw2 / cw3 = fp16 copies of color_mlp.params.
+ * Level arrays, the three aabbs (grid roi, scene, model) and bkgd[3] are HOST pointers; near_plane / far_plane are -inf / +inf when none.
+ * Outputs: rgb fp32 [n_rays,3], opacity / depth fp32 [n_rays], n_samples = one u64 (surviving samples, added to); n_samples and queue
+ * (8 bytes, the ray counter) are zeroed by the caller on `stream`.  Bit 63 of the queue word is set if the launch reached its pass bound. */
+int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, const uint8_t* binary, int rx, int ry, int rz, const uint32_t* coarse_bits,
+                    const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                    const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                    const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                    float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                    float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
