@@ -56,6 +56,8 @@ def config_parser(argv=None):
                    help="train: weight of an opt-in pose loss (mean L1 of the source key points moved by the predicted vs the true pose); 0 = the reference's step")
     p.add_argument("--pose_loss_layers", type=str, default="last", choices=["last", "all"],
                    help="train: decoder layers the pose loss supervises (the reference's losses read the last one)")
+    p.add_argument("--min_num_blocks", type=int, default=2, help="train_ngp_nerf.py --multi_blocks: fewest camera-cluster blocks per scene")
+    p.add_argument("--max_num_blocks", type=int, default=2, help="train_ngp_nerf.py --multi_blocks: most camera-cluster blocks per scene")
     args, _unknown = p.parse_known_args(argv)
     if isinstance(args.aabb, str):
         args.aabb = [float(v) for v in args.aabb.split(",")]

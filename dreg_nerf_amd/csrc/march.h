@@ -170,3 +170,113 @@ __device__ __forceinline__ bool march_density(bool have, const float (&x)[3], co
     march_wave_sync();
     return inside_m;
 }
+
+// ---- the renderer's per-ray setup and colour net, shared by the forward (render.hip) and the training backward (render_train.hip), which
+// re-marches every ray and must reproduce the forward's survivors and colours exactly.
+
+// Slab test of a ray against the scene aabb (t_min clamped at 0), then the near / far planes.  Returns whether the ray hits the aabb; the
+// caller still checks t_min < t_max (after its jitter, if any).
+__device__ __forceinline__ bool render_ray_interval(const float (&o)[3], const float (&d)[3], const float* scene, float near_plane, float far_plane,
+                                                    float& tmin, float& tmax)
+{
+    float near = -1e30f, far = 1e30f;
+    bool hit = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (d[k] == 0.f) { hit = hit && o[k] >= scene[k] && o[k] <= scene[3 + k]; continue; }   // parallel to the slab
+        const float id = 1.f / d[k];
+        float t0 = (scene[k] - o[k]) * id, t1 = (scene[3 + k] - o[k]) * id;
+        if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
+        near = fmaxf(near, t0); far = fminf(far, t1);
+    }
+    hit = hit && near <= far && far > 0.f;
+    tmin = fmaxf(fmaxf(near, 0.f), near_plane);
+    tmax = fminf(far, far_plane);
+    return hit;
+}
+
+// fp16 SH4(d) of a unit direction, two per word: the first 16 inputs of the colour net.
+__device__ __forceinline__ void render_sh4_f16(const float (&d)[3], uint32_t (&sh2)[8])
+{
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+    const float x = d[0], y = d[1], z = d[2];
+    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+    const float sh[16] = {0.28209479177387814f, -0.48860251190291987f * y, 0.48860251190291987f * z, -0.48860251190291987f * x,
+                          1.0925484305920792f * xy, -1.0925484305920792f * yz, 0.94617469575755997f * z2 - 0.31539156525251999f,
+                          -1.0925484305920792f * xz, 0.54627421529603959f * x2 - 0.54627421529603959f * y2,
+                          0.59004358992664352f * y * (-3.0f * x2 + y2), 2.8906114426405538f * xy * z,
+                          0.45704579946446572f * y * (1.0f - 5.0f * z2), 0.3731763325901154f * z * (5.0f * z2 - 3.0f),
+                          0.45704579946446572f * x * (1.0f - 5.0f * z2), 1.4453057213202769f * z * (x2 - y2),
+                          0.59004358992664352f * x * (-x2 + 3.0f * y2)};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const f16x2_t p = {(_Float16)sh[2 * j], (_Float16)sh[2 * j + 1]};
+        sh2[j] = __builtin_bit_cast(uint32_t, p);
+    }
+}
+
+// The colour net of the wave's 64 rows of sX (fp16 SH4(d) | 15 features | 1) -> relu 64 (sH1) -> relu 64 (sH2) -> 3 (sO[row*4 + ch], fp32 pre-
+// activation; channel 3 is padding), the arithmetic of ngp_rgb_kernel.  sH1 may equal sH2 (the forward's in-place second layer: a 16-row block
+// is read into registers in full before its outputs are written); the backward keeps both layers.  cw1f / cw3f: the first / last layer as
+// MFMA operands (fp16 [64][32] rows cb*16 + fr, [16][64] row fr), cw2: fp16 [64][64] in memory.
+__device__ __forceinline__ void march_color(char* sX, char* sH1, char* sH2, float* sO, const f16x8_t (&cw1f)[4], const _Float16* cw2,
+                                            const f16x8_t (&cw3f)[2], int lane)
+{
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+    const int fr = lane & 15, kg = lane >> 4;
+    march_wave_sync();
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * MARCH_XRS + kg * 16);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const f32x4_t v = __builtin_amdgcn_mfma_f32_16x16x32_f16(cw1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
+            f16x2_t p = {(_Float16)v[0], (_Float16)v[1]}, q = {(_Float16)v[2], (_Float16)v[3]};
+            p = __builtin_elementwise_max(p, z);
+            q = __builtin_elementwise_max(q, z);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(sH1 + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+            dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
+        }
+    }
+    march_wave_sync();
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        f16x8_t af[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) af[kb] = *reinterpret_cast<const f16x8_t*>(sH1 + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            f32x4_t h = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+                h = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(cw2 + (cb * 16 + fr) * 64 + kb * 32 + kg * 8), af[kb], h, 0, 0, 0);
+            const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
+            f16x2_t p = {(_Float16)h[0], (_Float16)h[1]}, q = {(_Float16)h[2], (_Float16)h[3]};
+            p = __builtin_elementwise_max(p, z);
+            q = __builtin_elementwise_max(q, z);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(sH2 + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+            dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
+        }
+    }
+    march_wave_sync();
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+            ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH2 + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2), cw3f[kb], ov, 0, 0, 0);
+        if (fr < 4) {        // channel fr of samples rb*16 + kg*4 + r (channel 3 is padding: written, never read)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sO[(rb * 16 + kg * 4 + r) * 4 + fr] = ov[r];
+        }
+    }
+    march_wave_sync();
+}
+
+// fp16 colour channel of a pre-activation (the forward's sigmoid, rounded as tcnn's fp16 output)
+__device__ __forceinline__ float march_sigmoid_f16(float pre)
+{
+    const float hv = (float)(_Float16)pre;
+    return (float)(_Float16)__builtin_amdgcn_rcpf(1.f + __expf(-hv));
+}

@@ -25,6 +25,7 @@
 struct RenderArgs {
     const float* origins;       // [N,3]
     const float* dirs;          // [N,3] unit viewing directions
+    const float* jitter;        // [N] per-ray u in [0,1) of stratified marching (dreg_ngp_render_train); null = 0 (dreg_ngp_render)
     long n_rays;
     const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
     const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]
@@ -54,7 +55,6 @@ __device__ __forceinline__ void render_write(const RenderArgs& a, long ray, cons
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ngp_render_kernel(RenderArgs a)
 {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
     __shared__ __attribute__((aligned(16))) char sX[64 * MARCH_XRS];
     __shared__ __attribute__((aligned(16))) char sH[64 * MARCH_HRS];
     __shared__ float sOut[64];
@@ -110,39 +110,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                     ray = (long)r;
 #pragma unroll
                     for (int k = 0; k < 3; ++k) { o[k] = a.origins[ray * 3 + k]; d[k] = a.dirs[ray * 3 + k]; }
-                    float near = -1e30f, far = 1e30f;
-                    bool hit = true;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        if (d[k] == 0.f) { hit = hit && o[k] >= a.scene[k] && o[k] <= a.scene[3 + k]; continue; }   // parallel to the slab
-                        const float id = 1.f / d[k];
-                        float t0 = (a.scene[k] - o[k]) * id, t1 = (a.scene[3 + k] - o[k]) * id;
-                        if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
-                        near = fmaxf(near, t0); far = fminf(far, t1);
-                    }
-                    hit = hit && near <= far && far > 0.f;
-                    tmin = fmaxf(fmaxf(near, 0.f), a.near);
-                    tmax = fminf(far, a.far);
+                    const bool hit = render_ray_interval(o, d, a.scene, a.near, a.far, tmin, tmax);
+                    if (a.jitter) tmin += a.jitter[ray] * a.dt;             // stratified marching (training): t_min + u dt, u in [0,1) per ray
                     const float acc0[3] = {0.f, 0.f, 0.f};
                     if (!hit || !(tmin < tmax)) render_write(a, ray, acc0, 0.f, 0.f);
                     else {
                         active = true; n = 0; T_all = 1.f; T_s = 1.f; opac = 0.f; dep = 0.f;
                         acc[0] = acc[1] = acc[2] = 0.f;
                         n_lim = (int)fminf(ceilf((tmax - tmin) / a.dt) + 1.f, (float)a.n_max);      // (a.n_max <= 1e8 + 2: the conversion cannot overflow)
-                        const float x = d[0], y = d[1], z = d[2];
-                        const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-                        const float sh[16] = {0.28209479177387814f, -0.48860251190291987f * y, 0.48860251190291987f * z, -0.48860251190291987f * x,
-                                              1.0925484305920792f * xy, -1.0925484305920792f * yz, 0.94617469575755997f * z2 - 0.31539156525251999f,
-                                              -1.0925484305920792f * xz, 0.54627421529603959f * x2 - 0.54627421529603959f * y2,
-                                              0.59004358992664352f * y * (-3.0f * x2 + y2), 2.8906114426405538f * xy * z,
-                                              0.45704579946446572f * y * (1.0f - 5.0f * z2), 0.3731763325901154f * z * (5.0f * z2 - 3.0f),
-                                              0.45704579946446572f * x * (1.0f - 5.0f * z2), 1.4453057213202769f * z * (x2 - y2),
-                                              0.59004358992664352f * x * (-x2 + 3.0f * y2)};
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const f16x2_t p = {(_Float16)sh[2 * j], (_Float16)sh[2 * j + 1]};
-                            sh2[j] = __builtin_bit_cast(uint32_t, p);
-                        }
+                        render_sh4_f16(d, sh2);
                     }
                 }
             }
@@ -179,64 +155,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         }
         if (__any(surv)) {
             // ---- colour of the surviving samples: X = (fp16 SH4(d) | 15 features | 1) -> relu 64 -> relu 64 -> 3, sigmoid (as ngp_rgb_kernel)
-            march_wave_sync();
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * MARCH_XRS + kg * 16);
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    const f32x4_t v = __builtin_amdgcn_mfma_f32_16x16x32_f16(cw1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
-                    f16x2_t p = {(_Float16)v[0], (_Float16)v[1]}, q = {(_Float16)v[2], (_Float16)v[3]};
-                    p = __builtin_elementwise_max(p, z);
-                    q = __builtin_elementwise_max(q, z);
-                    uint32_t* dst = reinterpret_cast<uint32_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
-                    dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
-                }
-            }
-            march_wave_sync();
-            // second layer in place: a 16-row block is read into registers in full before its outputs are written
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                f16x8_t af[2];
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) af[kb] = *reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2);
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    f32x4_t h = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-                        h = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(a.cw2 + (cb * 16 + fr) * 64 + kb * 32 + kg * 8), af[kb], h, 0, 0, 0);
-                    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
-                    f16x2_t p = {(_Float16)h[0], (_Float16)h[1]}, q = {(_Float16)h[2], (_Float16)h[3]};
-                    p = __builtin_elementwise_max(p, z);
-                    q = __builtin_elementwise_max(q, z);
-                    uint32_t* dst = reinterpret_cast<uint32_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
-                    dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
-                }
-            }
-            march_wave_sync();
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-                    ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2), cw3f[kb], ov, 0, 0, 0);
-                if (fr < 4) {        // channel fr of samples rb*16 + kg*4 + r (channel 3 is padding: written, never read)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sO[(rb * 16 + kg * 4 + r) * 4 + fr] = ov[r];
-                }
-            }
-            march_wave_sync();
+            march_color(sX, sH, sH, sO, cw1f, a.cw2, cw3f, lane);
             if (surv) {
                 const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
                 const float pv[3] = {pre.x, pre.y, pre.z};
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float hv = (float)(_Float16)pv[ch];
-                    const float c = (float)(_Float16)__builtin_amdgcn_rcpf(1.f + __expf(-hv));
-                    acc[ch] += w * c;
-                }
+                for (int ch = 0; ch < 3; ++ch) acc[ch] += w * march_sigmoid_f16(pv[ch]);
                 opac += w;
                 dep += w * tm;
                 ++my_samples;
@@ -254,17 +178,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (!finished && lane == 0) atomicOr(a.queue, 1ull << 63);
 }
 
-extern "C" {
-
-// Render n_rays rays of one block.  Caller-owned device buffers: origins / viewdirs fp32 [N,3], binary uint8 [rx,ry,rz], coarse_bits (optional),
-// the fp16 inference copies (table / w1 / w2 of mlp_base.params, cw1 / cw2 / cw3 of color_mlp.params), rgb fp32 [N,3], opacity / depth fp32 [N],
-// n_samples: one u64 and queue: 8 bytes, both zeroed by the caller on `stream`.  Level arrays, aabbs and bkgd are HOST pointers.
-int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, const uint8_t* binary, int rx, int ry, int rz, const uint32_t* coarse_bits,
-                    const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
-                    const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
-                    const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
-                    float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
-                    float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
+static int render_launch(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                         const uint32_t* coarse_bits, const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                         const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                         const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                         float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                         float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
 {
     if (n_rays < 0 || rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
     if (n_rays == 0) return DREG_OK;
@@ -272,7 +191,7 @@ int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, co
         !roi_aabb || !scene_aabb || !model_aabb || !bkgd || !rgb || !opacity || !depth || !n_samples || !queue)
         return DREG_EINVAL;
     RenderArgs a;
-    a.origins = origins; a.dirs = viewdirs; a.n_rays = n_rays;
+    a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
     a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
     a.cw1 = (const _Float16*)cw1; a.cw2 = (const _Float16*)cw2; a.cw3 = (const _Float16*)cw3;
     for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
@@ -295,6 +214,38 @@ int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, co
     hipLaunchKernelGGL(ngp_render_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
+}
+
+extern "C" {
+
+// Render n_rays rays of one block.  Caller-owned device buffers: origins / viewdirs fp32 [N,3], binary uint8 [rx,ry,rz], coarse_bits (optional),
+// the fp16 inference copies (table / w1 / w2 of mlp_base.params, cw1 / cw2 / cw3 of color_mlp.params), rgb fp32 [N,3], opacity / depth fp32 [N],
+// n_samples: one u64 and queue: 8 bytes, both zeroed by the caller on `stream`.  Level arrays, aabbs and bkgd are HOST pointers.
+int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, const uint8_t* binary, int rx, int ry, int rz, const uint32_t* coarse_bits,
+                    const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                    const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                    const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                    float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                    float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
+{
+    return render_launch(origins, viewdirs, nullptr, n_rays, binary, rx, ry, rz, coarse_bits, table, w1, w2, cw1, cw2, cw3, offset, size, res, scale, hashed,
+                         roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, early_stop_eps, bkgd,
+                         rgb, opacity, depth, n_samples, queue, stream);
+}
+
+// dreg_ngp_render with stratified marching (the training forward): ray i starts at t_min + jitter[i] * render_step_size, jitter fp32 [N] in [0,1)
+// on the device.  With jitter == 0 the results equal dreg_ngp_render's bit for bit.
+int dreg_ngp_render_train(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                          const uint32_t* coarse_bits, const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                          const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                          const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                          float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                          float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
+{
+    if (!jitter && n_rays > 0) return DREG_EINVAL;
+    return render_launch(origins, viewdirs, jitter, n_rays, binary, rx, ry, rz, coarse_bits, table, w1, w2, cw1, cw2, cw3, offset, size, res, scale, hashed,
+                         roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, early_stop_eps, bkgd,
+                         rgb, opacity, depth, n_samples, queue, stream);
 }
 
 #ifdef DREG_PROBE

@@ -1,0 +1,447 @@
+// Training of one NeRF block (Instant-NGP field + occupancy grid), gfx950: the backward of the volume renderer (render.hip) down to the hash
+// table, and the fused Adam step of the field.  The rule is the reference's training step (train_ngp_nerf.py:268-335 over nerfacc 0.3.5
+// ray_marching(stratified=True) + rendering), stated in DESIGN.md §3c; CPU restatement: tests/render_train_restatement.py.
+//
+// Backward of one ray, C its forward rgb (background included), g = dL/dC, survivors k with transmittance T_k, alpha_k, colour c_k, w_k = T_k alpha_k:
+//   dL/dc_k     = w_k g
+//   dL/dsigma_k = dt g . (T_{k+1} c_k - S_k),   S_k = C - sum_{j<=k} w_j c_j   (one forward sweep from the saved C)
+//   dL/dh0      = dL/dsigma exp(min(h0 - 1, 15))                  (trunc_exp; 0 outside the model aabb, where sigma = 0)
+// then through the sigmoid, the colour net (3 of its 16 outputs) into its 15 feature inputs, the density net, and the 16-level hash encoding
+// (trilinear corner weights) into the table.  Marched samples that do not survive get no gradient.
+//
+// ngp_render_bwd_kernel: one lane per ray.  The rays are cut into chunks that depend on n_rays only (64 rays each up to 131,072 rays); a wave takes
+// the next chunk from a queue and re-marches its rays with the forward's own helpers (march.h), so survivors and colours are those of the forward
+// bit for bit.  Per pass the wave's 64 samples go through the backward together:
+//   * per lane, fp32 on the VALU: the matrix-vector products of the chain (weights: fp32 copies of the fp16 inference copies, lane-uniform);
+//   * per wave, on MFMA (v_mfma_f32_16x16x4_f32, fp32): the weight gradients as sample-sum outer products (K = the wave's 64 samples), added into
+//     the chunk's own fp32 slab in global memory (the wave owns it: plain loads and stores);
+//   * per lane: the hash-table gradient, 16 levels x 8 corners x 2 fp32 global atomic adds (order free).
+// ngp_bwd_reduce_kernel then sums the slabs in chunk order: the MLP weight gradients are bit-identical across runs and launch widths.
+#include "march.h"
+#include "../../include/dreg_nerf.h"   // signature check of the entry points defined here
+
+// one slab = the five weight matrices in parameter order: density W1 [64][32], W2 [16][64] (= mlp_base.params[0:3072]), colour W1 [64][32],
+// W2 [64][64], W3 [16][64] (= color_mlp.params)
+constexpr int BWD_SLAB = 10240;
+constexpr int BWD_OFF_D1 = 0, BWD_OFF_D2 = 2048, BWD_OFF_C1 = 3072, BWD_OFF_C2 = 5120, BWD_OFF_C3 = 9216;
+constexpr long BWD_MAX_CHUNKS = 2048;
+constexpr int BWD_AS = 68;             // row stride (floats) of the wave's fp32 delta tile sA [64 samples][<= 64]
+
+struct RenderBwdArgs {
+    const float *origins, *dirs, *jitter;
+    long n_rays;
+    const _Float16 *table, *w1, *w2, *cw1, *cw2, *cw3;
+    const float* wf;                   // fp32 copies of the five weight matrices, slab layout
+    NgpLevelsV lv;
+    const uint8_t* binary;
+    const uint32_t* coarse;
+    int rx, ry, rz, cx, cy, cz;
+    float roi[6], scene[6], model[6];
+    float near, far, dt, alpha_thre, eps;
+    int n_max;
+    long pass_bound;                   // passes per chunk: chunk_rays * (n_max + 2) + 64
+    const float *rgb, *grad_rgb;       // forward rgb (with background) and dL/drgb, fp32 [N,3]
+    float* grad_table;                 // fp32 [entries][2], accumulated with atomics
+    float* slabs;                      // fp32 [n_chunks][BWD_SLAB], zeroed by the entry point
+    long chunk_rays;
+    int n_chunks;
+    unsigned int* queue;               // chunk counter, zeroed by the entry point
+};
+
+DREG_KNOB(int, g_render_bwd_waves, 2048);     // tuning (include/dreg_nerf_probe.h): one-wave workgroups of the backward launch; same results at every width
+
+static long bwd_chunk_rays(long n_rays)
+{
+    const long waves = (n_rays + 63) / 64;
+    return 64 * ((waves + BWD_MAX_CHUNKS - 1) / BWD_MAX_CHUNKS);
+}
+
+// W[m][n] += sum_s sA[s][m] X(s, n) over the wave's 64 samples, for the MT x NT 16x16 tiles of W (row stride ld) in the chunk's slab.  X(s, n) is
+// read from fp16 LDS rows and masked by sLive (rows of samples that did not survive are not read: they may hold anything).
+template <int MT, int NT>
+__device__ __forceinline__ void bwd_outer(float* slab, int ld, const float* sA, const char* sXin, int xrs, const float* sLive, int lane)
+{
+    const int fr = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int kk = 0; kk < 16; ++kk) {
+                const int s = kk * 4 + kq;
+                const float xv = sLive[s] != 0.f ? (float)reinterpret_cast<const _Float16*>(sXin + s * xrs)[nt * 16 + fr] : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sA[s * BWD_AS + mt * 16 + fr], xv, acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) slab[(mt * 16 + kq * 4 + r) * ld + nt * 16 + fr] += acc[r];    // W[mt*16 + kq*4 + r][nt*16 + fr]
+        }
+}
+
+__global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
+{
+    __shared__ __attribute__((aligned(16))) char sX[64 * MARCH_XRS];     // density input, then the colour input rows, then the encoding again
+    __shared__ __attribute__((aligned(16))) char sH[64 * MARCH_HRS];     // density hidden layer
+    __shared__ __attribute__((aligned(16))) char sH1[64 * MARCH_HRS];    // colour hidden layers
+    __shared__ __attribute__((aligned(16))) char sH2[64 * MARCH_HRS];
+    __shared__ __attribute__((aligned(16))) float sA[64 * BWD_AS];
+    __shared__ float sOut[64], sLive[64];
+    __shared__ __attribute__((aligned(16))) float sO[64 * 4];
+    __shared__ uint32_t sCoarse[1024];
+    const int lane = threadIdx.x;
+    const int fr = lane & 15, kg = lane >> 4;
+    const bool use_coarse = a.coarse != nullptr;
+    if (use_coarse) {
+        const int nw = (a.cx * a.cy * a.cz + 31) / 32;
+        for (int i = lane; i < nw; i += 64) sCoarse[i] = a.coarse[i];
+    }
+    __syncthreads();
+    MarchGrid g;
+    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
+    g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
+    MarchDensityW dw;
+    march_load_density_w(dw, a.w1, a.w2, lane);
+    f16x8_t cw1f[4], cw3f[2];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(a.cw3 + fr * 64 + kb * 32 + kg * 8);
+    const float* wd1 = a.wf + BWD_OFF_D1;
+    const float* wd2 = a.wf + BWD_OFF_D2;
+    const float* wc1 = a.wf + BWD_OFF_C1;
+    const float* wc2 = a.wf + BWD_OFF_C2;
+    const float* wc3 = a.wf + BWD_OFF_C3;
+
+    for (;;) {
+        unsigned int chunk = 0;
+        if (lane == 0) chunk = atomicAdd(a.queue, 1u);
+        chunk = __shfl(chunk, 0, 64);
+        if (chunk >= (unsigned int)a.n_chunks) break;
+        const long r0 = (long)chunk * a.chunk_rays;
+        const long r1 = min(a.n_rays, r0 + a.chunk_rays);
+        float* slab = a.slabs + (size_t)chunk * BWD_SLAB;
+        long next = r0;
+        bool active = false, exhausted = false;
+        long ray = 0;
+        int n = 0, n_lim = 0;
+        float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f}, tmin = 0.f, tmax = 0.f;
+        float T_all = 1.f, T_s = 1.f, acc[3] = {0.f, 0.f, 0.f}, C[3] = {0.f, 0.f, 0.f}, gr[3] = {0.f, 0.f, 0.f};
+        uint32_t sh2[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sh2[j] = 0u;
+
+        for (long it = 0; it < a.pass_bound; ++it) {
+            // ---- refill from the chunk's rays in lane order (no atomics: the chunk is this wave's)
+            for (int tries = 0; tries < 1024; ++tries) {
+                const bool need = !active && !exhausted;
+                const unsigned long long mask = __ballot(need);
+                if (!mask) break;
+                if (need) {
+                    const long r = next + (long)__popcll(mask & ((1ull << lane) - 1ull));
+                    if (r >= r1) exhausted = true;
+                    else {
+                        ray = r;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { o[k] = a.origins[ray * 3 + k]; d[k] = a.dirs[ray * 3 + k]; }
+                        const bool hit = render_ray_interval(o, d, a.scene, a.near, a.far, tmin, tmax);
+                        tmin += a.jitter[ray] * a.dt;
+                        if (hit && tmin < tmax) {
+                            active = true; n = 0; T_all = 1.f; T_s = 1.f;
+                            n_lim = (int)fminf(ceilf((tmax - tmin) / a.dt) + 1.f, (float)a.n_max);
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) { acc[k] = 0.f; C[k] = a.rgb[ray * 3 + k]; gr[k] = a.grad_rgb[ray * 3 + k]; }
+                            render_sh4_f16(d, sh2);
+                        }
+                    }
+                }
+                next += (long)__popcll(mask);
+            }
+            if (!__any(active)) {
+                if (__all(exhausted)) break;
+                continue;
+            }
+            // ---- the forward's march and density (march.h), sample for sample
+            float x[3] = {0.f, 0.f, 0.f}, tm = 0.f;
+            if (active && n >= n_lim) active = false;
+            const bool have = march_advance(g, o, d, tmin, tmax, a.dt, n, active, x, &tm, 4096);
+            if (!__any(have)) continue;
+            const bool inside_m = march_density<true>(have, x, a.model, a.lv, a.table, dw, sX, sH, sOut, lane);
+            bool surv = false;
+            float w = 0.f, h0 = 0.f;
+            if (have) {
+                h0 = sOut[lane];
+                const float sigma = inside_m ? __expf(h0 - 1.f) : 0.f;
+                const float alpha = 1.f - __expf(-sigma * a.dt);
+                surv = T_all >= a.eps && (a.alpha_thre <= 0.f || alpha >= a.alpha_thre);
+                T_all *= (1.f - alpha);
+                ++n;
+                if (surv) {
+                    w = alpha * T_s;
+                    T_s *= (1.f - alpha);                                 // = T_{k+1}
+                    uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * MARCH_XRS);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
+                    reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS)[31] = (_Float16)1.f;
+                }
+            }
+            if (__any(surv)) {
+                sLive[lane] = surv ? 1.f : 0.f;
+                march_color(sX, sH1, sH2, sO, cw1f, a.cw2, cw3f, lane);
+                // ---- this lane's survivor: dL/d(colour pre-activation) and dL/dh0
+                float dO[3] = {0.f, 0.f, 0.f}, dh0 = 0.f;
+                if (surv) {
+                    float dsig = 0.f;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const float c = march_sigmoid_f16(sO[lane * 4 + ch]);
+                        acc[ch] += w * c;
+                        dsig += gr[ch] * (T_s * c - (C[ch] - acc[ch]));
+                        dO[ch] = w * gr[ch] * c * (1.f - c);
+                    }
+                    dh0 = inside_m ? a.dt * dsig * __expf(fminf(h0 - 1.f, 15.f)) : 0.f;
+                }
+                float* rowA = sA + lane * BWD_AS;
+                // colour W3 (rows 0..2 of 16): dW3[c][i] += dO[c] h2[i]
+#pragma unroll
+                for (int c = 0; c < 16; ++c) rowA[c] = c < 3 ? dO[c] : 0.f;
+                march_wave_sync();
+                bwd_outer<1, 4>(slab + BWD_OFF_C3, 64, sA, sH2, MARCH_HRS, sLive, lane);
+                const _Float16* h2 = reinterpret_cast<const _Float16*>(sH2 + lane * MARCH_HRS);
+                const _Float16* h1 = reinterpret_cast<const _Float16*>(sH1 + lane * MARCH_HRS);
+                float d2[64];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) {
+                    const float s = wc3[i] * dO[0] + wc3[64 + i] * dO[1] + wc3[128 + i] * dO[2];
+                    d2[i] = (float)h2[i] > 0.f ? s : 0.f;
+                }
+                march_wave_sync();
+                // colour W2: dW2[j][i] += d2[j] h1[i]
+#pragma unroll
+                for (int j = 0; j < 64; ++j) rowA[j] = d2[j];
+                march_wave_sync();
+                bwd_outer<4, 4>(slab + BWD_OFF_C2, 64, sA, sH1, MARCH_HRS, sLive, lane);
+                float d1[64];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) d1[i] = 0.f;
+#pragma unroll
+                for (int j = 0; j < 64; ++j) {
+                    const float dj = d2[j];
+#pragma unroll
+                    for (int i = 0; i < 64; ++i) d1[i] += wc2[j * 64 + i] * dj;
+                }
+#pragma unroll
+                for (int i = 0; i < 64; ++i) d1[i] = (float)h1[i] > 0.f ? d1[i] : 0.f;
+                march_wave_sync();
+                // colour W1: dW1[i][k] += d1[i] x[k]; the 15 feature inputs (columns 16..30) carry the gradient on
+#pragma unroll
+                for (int i = 0; i < 64; ++i) rowA[i] = d1[i];
+                march_wave_sync();
+                bwd_outer<4, 2>(slab + BWD_OFF_C1, 32, sA, sX, MARCH_XRS, sLive, lane);
+                float dout[16];
+                dout[0] = dh0;
+#pragma unroll
+                for (int k = 1; k < 16; ++k) dout[k] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 64; ++i) {
+                    const float di = d1[i];
+#pragma unroll
+                    for (int k = 1; k < 16; ++k) dout[k] += wc1[i * 32 + 15 + k] * di;
+                }
+                march_wave_sync();
+                // density W2: dW2[o][i] += dout[o] hd[i]
+#pragma unroll
+                for (int k = 0; k < 16; ++k) rowA[k] = dout[k];
+                march_wave_sync();
+                bwd_outer<1, 4>(slab + BWD_OFF_D2, 64, sA, sH, MARCH_HRS, sLive, lane);
+                const _Float16* hd = reinterpret_cast<const _Float16*>(sH + lane * MARCH_HRS);
+                float dh[64];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) s += wd2[k * 64 + i] * dout[k];
+                    dh[i] = (float)hd[i] > 0.f ? s : 0.f;
+                }
+                float de[32];
+#pragma unroll
+                for (int k = 0; k < 32; ++k) de[k] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 64; ++i) {
+                    const float di = dh[i];
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) de[k] += wd1[i * 32 + k] * di;
+                }
+                march_wave_sync();
+#pragma unroll
+                for (int i = 0; i < 64; ++i) rowA[i] = dh[i];
+                // ---- hash encoding: the forward's corners again (march_density's arithmetic); the encoding goes back into sX for dW1 of the
+                // density net, the gradient into the table with one fp32 atomic add per corner and feature
+                if (surv) {
+                    float u[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        u[k] = (x[k] - a.model[k]) / (a.model[3 + k] - a.model[k]);
+                        u[k] = fminf(fmaxf(u[k], 0.f), 1.f);
+                    }
+                    _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS);
+#pragma unroll 2
+                    for (int l = 0; l < 16; ++l) {
+                        const float sc = a.lv.scale[l];
+                        const uint32_t res = a.lv.res[l], size = a.lv.size[l], hashed = a.lv.hashed[l];
+                        const _Float16* tl = a.table + (size_t)a.lv.offset[l] * 2;
+                        float* gl = a.grad_table + (size_t)a.lv.offset[l] * 2;
+                        float wt3[3];
+                        uint32_t gc[3];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { const float pos = u[k] * sc + 0.5f; const float fl = floorf(pos); gc[k] = (uint32_t)fl; wt3[k] = pos - fl; }
+                        float f0 = 0.f, f1 = 0.f;
+                        const float e0 = de[2 * l], e1 = de[2 * l + 1];
+#pragma unroll
+                        for (int corner = 0; corner < 8; ++corner) {
+                            const uint32_t cx = gc[0] + (corner & 1), cy = gc[1] + ((corner >> 1) & 1), cz = gc[2] + ((corner >> 2) & 1);
+                            const float wt = ((corner & 1) ? wt3[0] : 1.f - wt3[0]) * ((corner & 2) ? wt3[1] : 1.f - wt3[1]) * ((corner & 4) ? wt3[2] : 1.f - wt3[2]);
+                            const size_t idx = (size_t)vgrid_index(cx, cy, cz, res, size, hashed) * 2;
+                            union { uint32_t u32; _Float16 h[2]; } cv;
+                            cv.u32 = *reinterpret_cast<const uint32_t*>(tl + idx);
+                            f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
+                            unsafeAtomicAdd(gl + idx, wt * e0);
+                            unsafeAtomicAdd(gl + idx + 1, wt * e1);
+                        }
+                        xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
+                    }
+                }
+                march_wave_sync();
+                // density W1: dW1[i][k] += dh[i] enc[k]
+                bwd_outer<4, 2>(slab + BWD_OFF_D1, 32, sA, sX, MARCH_XRS, sLive, lane);
+            }
+            if (have && T_all < a.eps) active = false;           // transmittance below early_stop_eps: the ray ends
+            march_wave_sync();
+        }
+    }
+}
+
+// grad[e] += sum over chunks (in chunk order) of slab[c][e]: base = mlp_base.params[0:3072] gradient, color = color_mlp.params gradient
+__global__ void ngp_bwd_reduce_kernel(const float* __restrict__ slabs, int n_chunks, float* __restrict__ grad_base, float* __restrict__ grad_color)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= BWD_SLAB) return;
+    float s = 0.f;
+    for (int c = 0; c < n_chunks; ++c) s += slabs[(size_t)c * BWD_SLAB + e];
+    if (e < BWD_OFF_C1) grad_base[e] += s;
+    else grad_color[e - BWD_OFF_C1] += s;
+}
+
+__global__ void ngp_bwd_weights_kernel(const _Float16* __restrict__ base16, const _Float16* __restrict__ col16, float* __restrict__ wf)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= BWD_SLAB) return;
+    wf[e] = e < BWD_OFF_C1 ? (float)base16[e] : (float)col16[e - BWD_OFF_C1];
+}
+
+// torch.optim.Adam (single-tensor arithmetic, no weight decay) + the fp16 inference copy + a zeroed gradient, in one pass
+__global__ void ngp_adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, _Float16* __restrict__ p16,
+                                size_t n, float lr, float beta1, float beta2, float eps, float step_size, float bc2_sqrt)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float gi = g[i];
+        float mi = m[i], vi = v[i];
+        mi = mi + (1.f - beta1) * (gi - mi);                          // exp_avg.lerp_(grad, 1 - beta1)
+        vi = vi * beta2 + (1.f - beta2) * (gi * gi);                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        const float denom = __builtin_sqrtf(vi) / bc2_sqrt + eps;
+        const float pi = p[i] - step_size * (mi / denom);             // param.addcdiv_(exp_avg, denom, value=-step_size)
+        m[i] = mi; v[i] = vi; p[i] = pi;
+        p16[i] = (_Float16)pi;
+        g[i] = 0.f;
+    }
+}
+
+static int bwd_layout(long n_rays, long* chunk_rays, int* n_chunks, size_t* slab_off, size_t* queue_off, size_t* total)
+{
+    if (n_rays <= 0) return DREG_EINVAL;
+    *chunk_rays = bwd_chunk_rays(n_rays);
+    *n_chunks = (int)((n_rays + *chunk_rays - 1) / *chunk_rays);
+    *slab_off = (size_t)BWD_SLAB * sizeof(float);
+    *queue_off = *slab_off + (size_t)*n_chunks * BWD_SLAB * sizeof(float);
+    *total = *queue_off + 256;
+    return DREG_OK;
+}
+
+extern "C" {
+
+size_t dreg_ngp_render_bwd_workspace_bytes(long n_rays)
+{
+    long cr; int nc; size_t so, qo, tot;
+    return bwd_layout(n_rays, &cr, &nc, &so, &qo, &tot) == DREG_OK ? tot : 0;
+}
+
+int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                        const uint32_t* coarse_bits, const void* base16, const void* color16,
+                        const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                        const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                        float render_step_size, float alpha_thre, float early_stop_eps,
+                        const float* rgb, const float* grad_rgb, float* grad_base, float* grad_color, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (n_rays < 0 || rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
+    if (n_rays == 0) return DREG_OK;
+    if (!origins || !viewdirs || !jitter || !binary || !base16 || !color16 || !offset || !size || !res || !scale || !hashed || !roi_aabb || !scene_aabb ||
+        !model_aabb || !rgb || !grad_rgb || !grad_base || !grad_color || !workspace)
+        return DREG_EINVAL;
+    RenderBwdArgs a;
+    size_t slab_off, queue_off, total;
+    if (bwd_layout(n_rays, &a.chunk_rays, &a.n_chunks, &slab_off, &queue_off, &total) != DREG_OK || workspace_bytes < total) return DREG_EINVAL;
+    char* ws = (char*)workspace;
+    a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
+    const _Float16* b16 = (const _Float16*)base16;
+    const _Float16* c16 = (const _Float16*)color16;
+    a.w1 = b16; a.w2 = b16 + 2048; a.table = b16 + 3072;
+    a.cw1 = c16; a.cw2 = c16 + 2048; a.cw3 = c16 + 6144;
+    a.wf = (const float*)ws;
+    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
+    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
+    a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;
+    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
+    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;
+    a.near = near_plane; a.far = far_plane; a.dt = render_step_size; a.alpha_thre = alpha_thre; a.eps = early_stop_eps;
+    double diag = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = (double)scene_aabb[3 + k] - (double)scene_aabb[k]; diag += e * e; }
+    diag = __builtin_sqrt(diag);
+    if (!(diag >= 0.0) || diag / render_step_size > 1e8) return DREG_EINVAL;
+    a.n_max = (int)__builtin_ceil(diag / render_step_size) + 2;
+    const double passes = (double)a.chunk_rays * (double)(a.n_max + 2) + 64.0;
+    a.pass_bound = passes > 1e15 ? (long)1e15 : (long)passes;
+    a.rgb = rgb; a.grad_rgb = grad_rgb;
+    a.grad_table = grad_base + 3072;
+    a.slabs = (float*)(ws + slab_off);
+    a.queue = (unsigned int*)(ws + queue_off);
+    if (hipMemsetAsync(ws + slab_off, 0, total - slab_off, (hipStream_t)stream) != hipSuccess) return DREG_ELAUNCH;
+    hipLaunchKernelGGL(ngp_bwd_weights_kernel, dim3(BWD_SLAB / 256), dim3(256), 0, (hipStream_t)stream, b16, c16, (float*)ws);
+    DREG_LAUNCH_CHECK();
+    long waves = a.n_chunks;
+    if (waves > g_render_bwd_waves) waves = g_render_bwd_waves;
+    hipLaunchKernelGGL(ngp_render_bwd_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
+    DREG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ngp_bwd_reduce_kernel, dim3(BWD_SLAB / 256), dim3(256), 0, (hipStream_t)stream, (const float*)(ws + slab_off), a.n_chunks,
+                       grad_base, grad_color);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+int dreg_ngp_adam_step(float* p, float* g, float* m, float* v, void* p16, size_t n, float lr, float beta1, float beta2, float eps, int step, void* stream)
+{
+    if (n == 0) return DREG_OK;
+    if (!p || !g || !m || !v || !p16 || step < 1) return DREG_EINVAL;
+    const double bc1 = 1.0 - __builtin_pow((double)beta1, (double)step), bc2 = 1.0 - __builtin_pow((double)beta2, (double)step);
+    size_t b = (n + 255) / 256; if (b > 8192) b = 8192;
+    hipLaunchKernelGGL(ngp_adam_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (_Float16*)p16, n, lr, beta1, beta2, eps,
+                       (float)(lr / bc1), (float)__builtin_sqrt(bc2));
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+#ifdef DREG_PROBE
+void dreg_render_bwd_set_waves(int n) { g_render_bwd_waves = n > 0 ? n : 2048; }
+#endif
+
+}  // extern "C"

@@ -241,6 +241,11 @@ SIGNATURES = {
     "dreg_surface_visibility_multi_waves": (I, [P, I, ctypes.c_long, I, P]),
     # render.hip
     "dreg_ngp_render": (I, [P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
+    # render_train.hip
+    "dreg_ngp_render_train": (I, [P, P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
+    "dreg_ngp_render_bwd_workspace_bytes": (Z, [ctypes.c_long]),
+    "dreg_ngp_render_bwd": (I, [P, P, P, ctypes.c_long, P, I, I, I, P, P, P] + [P] * 5 + [P, P, P] + [F] * 5 + [P, P, P, P, P, Z, P]),
+    "dreg_ngp_adam_step": (I, [P] * 5 + [Z, F, F, F, F, I, P]),
 }
 
 
@@ -279,6 +284,7 @@ PROBE_SIGNATURES = {
     "dreg_visibility_set_waves": (None, [I]),
     "dreg_visibility_set_pass_bound": (I, [ctypes.c_long]),
     "dreg_render_set_waves": (None, [I]),
+    "dreg_render_bwd_set_waves": (None, [I]),
 }
 PROBE_LIB_PATH = os.path.join(_HERE, "libdreg_nerf_hip_probe.so")
 _probe_lib = None

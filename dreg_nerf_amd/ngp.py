@@ -255,8 +255,9 @@ def sh4(d: torch.Tensor) -> torch.Tensor:
 class OccupancyGrid(nn.Module):
     """State holder for a nerfacc 0.3.5 ``OccupancyGrid`` (the 'occupancy_grid' entry of a NeRF block checkpoint,
     train_ngp_nerf.py:196; constructed as in conerf/loss/confidence_loss.py:42-46).  Persistent buffers of the original: _roi_aabb
-    fp32 [6], resolution int32 [3], occs fp32 [res^3] (the EMA densities), _binary bool [res,res,res].  Training the grid
-    (every_n_step) belongs to NeRF training, which is out of scope; the registration path only reads ``binary``."""
+    fp32 [6], resolution int32 [3], occs fp32 [res^3] (the EMA densities), _binary bool [res,res,res].  The registration path only reads
+    ``binary``; NeRF training (dreg_nerf_amd/ngp_train.py) updates the grid with every_n_step, nerfacc 0.3.5's rule, in training
+    mode only."""
     NUM_DIM = 3
     _NON_PERSISTENT = ("grid_coords", "grid_indices")   # written by some nerfacc builds, rebuilt on construction there
 
@@ -290,6 +291,46 @@ class OccupancyGrid(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True):
         sd = {k: v for k, v in state_dict.items() if k not in self._NON_PERSISTENT}
         return super().load_state_dict(sd, strict=strict)
+
+    @torch.no_grad()
+    def _sample_cells(self, step: int, warmup_steps: int) -> torch.Tensor:
+        """Flat indices of the cells to update: all of them before warmup_steps; after, num_cells // 4 uniform random cells followed by up to
+        num_cells // 4 cells drawn at random from the occupied ones (all of them when fewer are occupied)."""
+        dev = self.occs.device
+        if step < warmup_steps:
+            return torch.arange(self.num_cells, device=dev)
+        n = self.num_cells // 4
+        uniform = torch.randint(self.num_cells, (n,), device=dev)
+        occupied = torch.nonzero(self._binary.flatten())[:, 0]
+        if n < len(occupied):
+            occupied = occupied[torch.randint(len(occupied), (n,), device=dev)]
+        return torch.cat([uniform, occupied], dim=0)
+
+    @torch.no_grad()
+    def _update(self, step: int, occ_eval_fn, occ_thre: float = 1e-2, ema_decay: float = 0.95, warmup_steps: int = 256):
+        """One update (nerfacc 0.3.5 OccupancyGrid._update, AABB contraction): a jittered point per chosen cell, occ = occ_eval_fn(x),
+        occs[idx] = max(occs[idx] * ema_decay, occ) (an index drawn twice: either write wins), binary = occs > min(mean(occs), occ_thre)."""
+        if getattr(self._contraction_type, "name", "AABB") != "AABB":
+            raise NotImplementedError("OccupancyGrid._update: only ContractionType.AABB")
+        idx = self._sample_cells(step, warmup_steps)
+        rx, ry, rz = (int(v) for v in self.resolution.tolist())
+        coords = torch.stack([idx // (ry * rz), (idx // rz) % ry, idx % rz], dim=-1).float()
+        res = torch.tensor([rx, ry, rz], dtype=torch.float32, device=idx.device)
+        u = (coords + torch.rand_like(coords)) / res
+        lo, hi = self._roi_aabb[:3].to(idx.device), self._roi_aabb[3:].to(idx.device)
+        x = u * (hi - lo) + lo
+        occ = occ_eval_fn(x).reshape(-1).float()
+        self.occs[idx] = torch.maximum(self.occs[idx] * ema_decay, occ)
+        self._binary = (self.occs > torch.clamp(self.occs.mean(), max=occ_thre)).view(self._binary.shape)
+
+    @torch.no_grad()
+    def every_n_step(self, step: int, occ_eval_fn, occ_thre: float = 1e-2, ema_decay: float = 0.95, warmup_steps: int = 256, n: int = 16):
+        """nerfacc 0.3.5 OccupancyGrid.every_n_step: _update when step % n == 0.  Training mode only (call _update directly otherwise)."""
+        if not self.training:
+            raise RuntimeError("You should only call this function only during training. Please call _update() directly if you want to update the "
+                               "field during inference.")
+        if step % n == 0:
+            self._update(step, occ_eval_fn, occ_thre, ema_decay, warmup_steps)
 
     @torch.no_grad()
     def query_occ(self, samples: torch.Tensor) -> torch.Tensor:

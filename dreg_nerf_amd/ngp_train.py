@@ -1,0 +1,188 @@
+"""Training of one NeRF block (the reference's train_ngp_nerf.py:268-335, conerf/utils/utils.py:44-141), rule in DESIGN.md §3c:
+
+  render_image_train   the renderer with stratified marching (csrc/render.hip dreg_ngp_render_train) as an autograd Function whose backward is
+                       csrc/render_train.hip dreg_ngp_render_bwd: rgb is differentiable w.r.t. mlp_base.params and color_mlp.params
+  NGPAdam              torch.optim.Adam(lr=1e-2, eps=1e-15) whose step is one fused pass per parameter (dreg_ngp_adam_step) that also refreshes the
+                       field's fp16 inference copies and zeroes the gradient; state_dict layout = torch.optim.Adam's
+  NGPTrainer           the per-step rule: occupancy update every 16 steps, random rays over the block's images, render, smooth-L1 on the alive
+                       rays, Adam, MultiStepLR, and the adaptive ray count that keeps 2^18 rendered samples per step
+"""
+import ctypes
+import math
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import lib as L
+from . import ngp
+from . import render as R
+
+TARGET_SAMPLES = 1 << 18
+_LAST = {"n": 0}          # surviving samples of the last training forward
+
+
+def render_step_size_of(aabb) -> float:
+    """max(aabb extent) sqrt(3) / 1024 (train_ngp_nerf.py, AABB scenes)."""
+    a = [float(v) for v in (aabb.tolist() if torch.is_tensor(aabb) else aabb)]
+    return max(a[3] - a[0], a[4] - a[1], a[5] - a[2]) * math.sqrt(3) / 1024
+
+
+def _f6(v):
+    return (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
+
+
+class _RenderTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, base_params, color_params, field, occupancy_grid, o, d, jitter, scene_aabb, dt, bkgd, alpha_thre):
+        lib = L.load()
+        base16, col16 = field._prepared()
+        dev = base16.device
+        n = o.shape[0]
+        roi, b8, bits = R._grid_parts(occupancy_grid, dev)
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        opacity = torch.empty(n, dtype=torch.float32, device=dev)
+        depth = torch.empty(n, dtype=torch.float32, device=dev)
+        counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        L.check(lib.dreg_ngp_render_train(L.ptr(o), L.ptr(d), L.ptr(jitter), n, L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
+                                          base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+                                          col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
+                                          *field._levels, _f6(roi), _f6(scene_aabb), _f6(field._aabb_host()), -math.inf, math.inf,
+                                          float(dt), float(alpha_thre), 1e-4, (ctypes.c_float * 3)(*bkgd),
+                                          L.ptr(rgb), L.ptr(opacity), L.ptr(depth), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
+                "dreg_ngp_render_train")
+        c = counters.cpu()                      # the step's one readback: the surviving samples (next step's ray count)
+        if int(c[1]) < 0:
+            raise RuntimeError("dreg_ngp_render_train reached its pass bound")
+        _LAST["n"] = int(c[0])
+        ctx.field, ctx.grid_parts, ctx.scene_aabb, ctx.dt, ctx.alpha_thre = field, (roi, b8, bits), scene_aabb, float(dt), float(alpha_thre)
+        ctx.save_for_backward(o, d, jitter, rgb)
+        ctx.mark_non_differentiable(opacity, depth)
+        return rgb, opacity, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, _g_op, _g_dep):
+        lib = L.load()
+        o, d, jitter, rgb = ctx.saved_tensors
+        field = ctx.field
+        base16, col16 = field._prepared()
+        dev = base16.device
+        roi, b8, bits = ctx.grid_parts
+        n = o.shape[0]
+        grad_base = torch.zeros(base16.numel(), dtype=torch.float32, device=dev)
+        grad_color = torch.zeros(col16.numel(), dtype=torch.float32, device=dev)
+        if n and g_rgb is not None:
+            nws = int(lib.dreg_ngp_render_bwd_workspace_bytes(n))
+            ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+            L.check(lib.dreg_ngp_render_bwd(L.ptr(o), L.ptr(d), L.ptr(jitter), n, L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
+                                            base16.data_ptr(), col16.data_ptr(), *field._levels, _f6(roi), _f6(ctx.scene_aabb), _f6(field._aabb_host()),
+                                            -math.inf, math.inf, ctx.dt, ctx.alpha_thre, 1e-4, L.ptr(rgb), L.ptr(g_rgb.float().contiguous()),
+                                            L.ptr(grad_base), L.ptr(grad_color), L.ptr(ws), nws, L.stream()), "dreg_ngp_render_bwd")
+        return grad_base, grad_color, None, None, None, None, None, None, None, None, None
+
+
+def render_image_train(field, occupancy_grid, rays, scene_aabb, render_step_size: float, render_bkgd=None, alpha_thre: float = 0.0,
+                       jitter: Optional[torch.Tensor] = None):
+    """render_image for training (stratified marching, differentiable rgb): rays with origins / viewdirs [N,3] -> (rgb [N,3], opacity [N,1],
+    depth [N,1], n_rendering_samples int).  jitter fp32 [N] in [0,1) (the per-ray offset u of t_min + u dt) is drawn with torch.rand when not
+    given.  Opacity and depth are detached."""
+    if getattr(field, "unbounded", False) or scene_aabb is None:
+        raise NotImplementedError("render_image_train: unbounded scenes are not supported")
+    if getattr(getattr(occupancy_grid, "contraction_type", None), "name", "AABB") != "AABB":
+        raise NotImplementedError("render_image_train: only ContractionType.AABB occupancy grids")
+    base16, _ = field._prepared()
+    dev = base16.device
+    o = rays.origins.reshape(-1, 3).to(dev).float().contiguous()
+    d = rays.viewdirs.reshape(-1, 3).to(dev).float().contiguous()
+    n = o.shape[0]
+    if jitter is None:
+        jitter = torch.rand(n, dtype=torch.float32, device=dev)
+    jitter = jitter.to(dev).float().contiguous()
+    bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(v) for v in torch.as_tensor(render_bkgd).reshape(-1).tolist()]
+    rgb, opacity, depth = _RenderTrain.apply(field.mlp_base.params, field.color_mlp.params, field, occupancy_grid, o, d, jitter,
+                                             [float(v) for v in (scene_aabb.tolist() if torch.is_tensor(scene_aabb) else scene_aabb)],
+                                             float(render_step_size), bk, float(alpha_thre or 0.0))
+    return rgb, opacity[:, None], depth[:, None], _LAST["n"]
+
+
+class NGPAdam(torch.optim.Adam):
+    """torch.optim.Adam(field.parameters(), lr, betas, eps) with a fused step: one pass per parameter updates p, exp_avg and exp_avg_sq, writes the
+    field's fp16 inference copy (the buffers its renderer reads) and zeroes p.grad.  Same state_dict as torch.optim.Adam."""
+
+    def __init__(self, field: ngp.NGPradianceField, lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-15):
+        super().__init__([field.mlp_base.params, field.color_mlp.params], lr=lr, betas=betas, eps=eps, foreach=False)
+        self.field = field
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        assert closure is None
+        lib = L.load()
+        base16, col16 = self.field._prepared()
+        copies = {id(self.field.mlp_base.params): base16, id(self.field.color_mlp.params): col16}
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+                g = p.grad
+                assert g.is_contiguous() and g.dtype == torch.float32
+                L.check(lib.dreg_ngp_adam_step(L.ptr(p.data), L.ptr(g), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), copies[id(p)].data_ptr(),
+                                               p.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(st["step"].item()),
+                                               L.stream()), "dreg_ngp_adam_step")
+        return None
+
+
+def multistep_lr(optimizer, max_iterations: int):
+    """MultiStepLR(milestones=[max_it // 2, max_it * 3 // 4, max_it * 9 // 10], gamma=0.33) of train_ngp_nerf.py."""
+    return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[max_iterations // 2, max_iterations * 3 // 4, max_iterations * 9 // 10],
+                                                gamma=0.33)
+
+
+def next_num_rays(num_rays: int, n_samples: int, target: int = TARGET_SAMPLES) -> int:
+    """The ray count of the next step: int(num_rays * target / n_rendering_samples)."""
+    return int(num_rays * (target / float(n_samples)))
+
+
+class NGPTrainer:
+    """The per-step rule of train_ngp_nerf.py for one AABB block."""
+
+    def __init__(self, field: ngp.NGPradianceField, grid: ngp.OccupancyGrid, data, aabb, max_iterations: int,
+                 target_sample_batch_size: int = TARGET_SAMPLES):
+        self.field, self.grid, self.data = field, grid, data
+        self.aabb = [float(v) for v in (aabb.tolist() if torch.is_tensor(aabb) else aabb)]
+        self.render_step_size = render_step_size_of(self.aabb)
+        self.alpha_thre = 0.0
+        self.target = int(target_sample_batch_size)
+        self.num_rays = self.target // 1024
+        self.optimizer = NGPAdam(field, lr=1e-2, eps=1e-15)
+        self.scheduler = multistep_lr(self.optimizer, max_iterations)
+        self.bkgd = torch.ones(3, dtype=torch.float32)
+        self.last = {}
+
+    def occ_eval_fn(self, x):
+        return self.field.query_density(x) * self.render_step_size
+
+    def step(self, it: int):
+        """One training iteration; returns the loss (float) or None when no sample survived (the step is skipped)."""
+        self.field.train()
+        self.grid.train()
+        self.grid.every_n_step(step=it, occ_eval_fn=self.occ_eval_fn, occ_thre=1e-2)
+        rays, pixels = self.data.sample(self.num_rays)
+        rgb, opacity, _depth, n = render_image_train(self.field, self.grid, rays, self.aabb, self.render_step_size, self.bkgd, self.alpha_thre)
+        if n == 0:
+            return None
+        self.num_rays = max(1, next_num_rays(len(pixels), n, self.target))
+        alive = opacity.squeeze(-1) > 0
+        loss = F.smooth_l1_loss(rgb[alive], pixels[alive])
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        self.scheduler.step()
+        self.last = {"loss": float(loss.detach()), "n_samples": n, "num_rays": len(pixels), "alive": int(alive.sum())}
+        return self.last["loss"]

@@ -731,6 +731,32 @@ int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, co
                     float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
                     float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- training of a NeRF block
+ * (csrc/render.hip, csrc/render_train.hip; rule: DESIGN.md §3c).
+ * dreg_ngp_render_train = dreg_ngp_render with stratified marching: ray i starts at t_min + jitter[i] * render_step_size, jitter fp32 [n_rays]
+ * in [0,1) on the device (required).  jitter == 0 gives dreg_ngp_render's results bit for bit.
+ * dreg_ngp_render_bwd: the backward of that forward for dL/drgb = grad_rgb fp32 [n_rays,3], given its rgb output and the same jitter.  base16 /
+ * color16 = the fp16 inference copies of mlp_base.params / color_mlp.params.  Gradients are ADDED: grad_base fp32 [numel(mlp_base.params)] (the
+ * MLP part [0,3072) from per-chunk slabs reduced in a fixed order: bit-identical between runs and launch widths; the hash table [3072,..) with
+ * fp32 atomic adds), grad_color fp32 [7168].  Directions get no gradient.  workspace: dreg_ngp_render_bwd_workspace_bytes(n_rays) bytes of
+ * device memory (cleared by the call on `stream`).
+ * dreg_ngp_adam_step: torch.optim.Adam (no weight decay, no amsgrad) on n fp32 parameters at the given lr and step (>= 1, bias correction),
+ * writes p16 = fp16(p) (dreg_f32_to_f16's rounding) and zeroes g, in one pass. */
+int dreg_ngp_render_train(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                          const uint32_t* coarse_bits, const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                          const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                          const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                          float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                          float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream);
+size_t dreg_ngp_render_bwd_workspace_bytes(long n_rays);
+int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                        const uint32_t* coarse_bits, const void* base16, const void* color16,
+                        const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                        const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                        float render_step_size, float alpha_thre, float early_stop_eps,
+                        const float* rgb, const float* grad_rgb, float* grad_base, float* grad_color, void* workspace, size_t workspace_bytes, void* stream);
+int dreg_ngp_adam_step(float* p, float* g, float* m, float* v, void* p16, size_t n, float lr, float beta1, float beta2, float eps, int step, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs

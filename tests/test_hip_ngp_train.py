@@ -1,0 +1,286 @@
+"""NeRF block training on the GPU: the stratified training forward, the fused backward against CPU autograd over the oracle's
+networks, determinism of the MLP gradients, the fused Adam step, and train_ngp_nerf.py end to end on a synthetic sphere."""
+import json
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+pytestmark = pytest.mark.gpu
+
+AABB = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5]
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda:0")
+
+
+def _block(dev, seed=0, res=32, radius=0.8, table_scale=1.0):
+    """A field with a table of U(-table_scale, table_scale) (density and colour that vary along a ray) and a ball-shaped occupancy grid."""
+    from dreg_nerf_amd import ngp
+    torch.manual_seed(seed)
+    f = ngp.NGPradianceField(AABB)
+    with torch.no_grad():
+        f.mlp_base.params[3072:].uniform_(-table_scale, table_scale)
+    f = f.to(dev)
+    g = ngp.OccupancyGrid(AABB, res).to(dev)
+    c = (torch.stack(torch.meshgrid(*[torch.arange(res)] * 3, indexing="ij"), -1).float() + 0.5) / res * 3.0 - 1.5
+    g._binary = (c.norm(dim=-1) < radius).to(dev)
+    return f, g
+
+
+def _rays(n, seed=1, dist=3.5):
+    gen = torch.Generator().manual_seed(seed)
+    o = torch.nn.functional.normalize(torch.randn(n, 3, generator=gen), dim=-1) * dist
+    tgt = (torch.rand(n, 3, generator=gen) - 0.5) * 1.2
+    d = torch.nn.functional.normalize(tgt - o, dim=-1)
+    from dreg_nerf_amd.render import Rays
+    return Rays(o, d)
+
+
+def test_train_forward_zero_jitter_equals_render_bitwise():
+    dev = _dev()
+    from dreg_nerf_amd import ngp_train, render
+    f, g = _block(dev)
+    rays = _rays(3000)
+    rays_d = render.Rays(rays.origins.to(dev), rays.viewdirs.to(dev))
+    dt = ngp_train.render_step_size_of(AABB)
+    bk = torch.ones(3)
+    f.eval()
+    with torch.no_grad():
+        ref = render.render_image(f, g, rays_d, AABB, render_step_size=dt, render_bkgd=bk)
+    f.train()
+    out = ngp_train.render_image_train(f, g, rays_d, AABB, dt, bk, jitter=torch.zeros(3000, device=dev))
+    for a, b in zip(out[:3], ref[:3]):
+        assert torch.equal(a.detach().reshape(-1), b.reshape(-1))
+    assert out[3] == ref[3] > 0
+
+
+def _cpu_reference(f, g, rays, jitter, dt, bkgd, g_rgb, mask):
+    import render_train_restatement as RT
+    base = f.mlp_base.params.detach().cpu().clone().requires_grad_(True)
+    color = f.color_mlp.params.detach().cpu().clone().requires_grad_(True)
+    rgb, opac, depth, surv = RT.render_train(base, color, AABB, rays.origins, rays.viewdirs, g.binary.cpu(), AABB, AABB, dt, jitter.cpu(), bkgd)
+    (rgb * (g_rgb * mask[:, None])).sum().backward()
+    return rgb.detach(), opac.detach(), base.grad, color.grad, surv
+
+
+def test_backward_matches_cpu_autograd():
+    """GPU gradients against autograd through the restatement over oracle.ngp_oracle, on the rays whose forward agrees (>= 99 %).
+    Tolerances: the kernel and the oracle share the fp16 forward (table, weights, activations rounded to fp16, fp32 sums); they differ in the
+    order of the fp32 sums and in the backward's own arithmetic (fp32 on the GPU, fp32 autograd through fp16-rounded values on the CPU), so the
+    MLP gradients must agree to cosine >= 0.999 and relative L2 <= 2e-2, the table gradient on touched entries to relative L2 <= 2e-2."""
+    dev = _dev()
+    from dreg_nerf_amd import ngp_train, render
+    f, g = _block(dev, seed=3)
+    n = 300
+    rays = _rays(n, seed=4)
+    dt = 0.02
+    bk = torch.ones(3)
+    jitter = torch.rand(n, generator=torch.Generator().manual_seed(5))
+    g_rgb = torch.randn(n, 3, generator=torch.Generator().manual_seed(6)) / n
+    f.train()
+    rays_d = render.Rays(rays.origins.to(dev), rays.viewdirs.to(dev))
+    rgb, opac, _, ns = ngp_train.render_image_train(f, g, rays_d, AABB, dt, bk, jitter=jitter.to(dev))
+    rgb_c, opac_c, _, _, surv_c = _cpu_reference(f, g, rays, jitter, dt, bk, torch.zeros(n, 3), torch.zeros(n))
+    # survivors per ray on the GPU: one launch per ray (the kernel reports the total only)
+    with torch.no_grad():
+        per_ray = torch.tensor([ngp_train.render_image_train(f, g, render.Rays(rays_d.origins[i:i + 1], rays_d.viewdirs[i:i + 1]), AABB, dt, bk,
+                                                             jitter=jitter[i:i + 1].to(dev))[3] for i in range(n)])
+    assert int(per_ray.sum()) == ns
+    agree = (per_ray == surv_c.sum(1)) & ((rgb.detach().cpu() - rgb_c).abs().max(-1).values < 2e-3)
+    assert agree.float().mean() >= 0.99, f"forward agrees on {agree.float().mean():.3f} of the rays"
+    mask = agree.float()
+    f.mlp_base.params.grad = None
+    f.color_mlp.params.grad = None
+    (rgb * (g_rgb.to(dev) * mask.to(dev)[:, None])).sum().backward()
+    gb, gc = f.mlp_base.params.grad.cpu(), f.color_mlp.params.grad.cpu()
+    _, _, rb, rc, _ = _cpu_reference(f, g, rays, jitter, dt, bk, g_rgb, mask)
+
+    def close(a, b, what, cos_min=0.999, rel=2e-2):
+        cos = torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), b.double().reshape(1, -1)).item()
+        r = ((a.double() - b.double()).norm() / b.double().norm()).item()
+        assert cos >= cos_min and r <= rel, f"{what}: cosine {cos:.5f}, rel L2 {r:.3e}"
+
+    close(gb[:2048], rb[:2048], "density W1")
+    close(gb[2048:3072], rb[2048:3072], "density W2")
+    close(gc[:2048], rc[:2048], "colour W1")
+    close(gc[2048:6144], rc[2048:6144], "colour W2")
+    close(gc[6144:6144 + 192], rc[6144:6144 + 192], "colour W3 (rgb rows)")
+    assert torch.count_nonzero(gc[6144 + 192:]) == 0
+    import render_train_restatement as RT
+    touched = RT.reached_entries(agree)
+    close(gb[3072:][touched], rb[3072:][touched], "hash table (touched)")
+    # untouched entries are 0, save corners whose sample position differs from the CPU's by an ulp and falls across a cell face with a
+    # trilinear weight below ~1e-5 (measured: 26 of 2.9 M entries, <= 2.5e-6 of the largest gradient)
+    stray = (gb[3072:] != 0) & ~touched
+    assert int(stray.sum()) <= 1e-3 * int(touched.sum()), int(stray.sum())
+    assert int(stray.sum()) == 0 or gb[3072:][stray].abs().max() <= 1e-5 * gb[3072:][touched].abs().max()
+
+
+def test_backward_mlp_gradients_deterministic_across_runs_and_widths():
+    dev = _dev()
+    from dreg_nerf_amd import lib as L, ngp_train, render
+    f, g = _block(dev, seed=7)
+    n = 5000
+    rays = _rays(n, seed=8)
+    rays_d = render.Rays(rays.origins.to(dev), rays.viewdirs.to(dev))
+    jitter = torch.rand(n, device=dev)
+    dt = ngp_train.render_step_size_of(AABB)
+    g_rgb = torch.randn(n, 3, device=dev)
+    f.train()
+
+    def grads():
+        f.mlp_base.params.grad = None
+        f.color_mlp.params.grad = None
+        rgb, _, _, _ = ngp_train.render_image_train(f, g, rays_d, AABB, dt, torch.ones(3), jitter=jitter)
+        (rgb * g_rgb).sum().backward()
+        return f.mlp_base.params.grad.clone(), f.color_mlp.params.grad.clone()
+
+    b0, c0 = grads()
+    b1, c1 = grads()
+    assert torch.equal(b0[:3072], b1[:3072]) and torch.equal(c0, c1)
+    with L.probe() as p:
+        for w in (1, 7, 300):
+            p.set("dreg_render_bwd_set_waves", w, 2048)
+            bw, cw = grads()
+            assert torch.equal(b0[:3072], bw[:3072]) and torch.equal(c0, cw), f"width {w}"
+            # the table: fp32 atomics in any order; the coarse levels sum ~10^5 adds of both signs per entry, so the reassociation error is
+            # absolute, a few 1e-7 here: bounded by 1e-5 of the largest entry
+            torch.testing.assert_close(bw[3072:], b0[3072:], rtol=1e-4, atol=1e-5 * float(b0[3072:].abs().max()))
+    assert c0.abs().sum() > 0 and b0[3072:].abs().sum() > 0
+
+
+def test_fused_adam_matches_torch_adam():
+    dev = _dev()
+    from dreg_nerf_amd import lib as L, ngp, ngp_train
+    torch.manual_seed(11)
+    f = ngp.NGPradianceField(AABB).to(dev)
+    ref = [f.mlp_base.params.detach().clone(), f.color_mlp.params.detach().clone()]
+    ref = [torch.nn.Parameter(r) for r in ref]
+    opt_ref = torch.optim.Adam(ref, lr=1e-2, eps=1e-15)
+    opt = ngp_train.NGPAdam(f, lr=1e-2, eps=1e-15)
+    for step in range(5):
+        gs = [torch.randn_like(r) * (10.0 ** -step) for r in ref]
+        for r, gr in zip(ref, gs):
+            r.grad = gr.clone()
+        f.mlp_base.params.grad = gs[0].clone()
+        f.color_mlp.params.grad = gs[1].clone()
+        opt_ref.step()
+        opt.step()
+        torch.testing.assert_close(f.mlp_base.params.detach(), ref[0].detach(), rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(f.color_mlp.params.detach(), ref[1].detach(), rtol=1e-5, atol=1e-6)
+        assert torch.count_nonzero(f.mlp_base.params.grad) == 0 and torch.count_nonzero(f.color_mlp.params.grad) == 0
+    base16, col16 = f._prepared()
+    for p, c in ((f.mlp_base.params, base16), (f.color_mlp.params, col16)):
+        want = torch.empty_like(c)
+        L.check(L.load().dreg_f32_to_f16(L.ptr(p.detach()), L.ptr(want), want.numel(), L.stream()), "dreg_f32_to_f16")
+        assert torch.equal(c, want)
+    sd = opt.state_dict()
+    assert set(sd["state"][0]) == {"step", "exp_avg", "exp_avg_sq"} and float(sd["state"][0]["step"]) == 5.0
+    opt_ref.load_state_dict(sd)           # the layout torch.optim.Adam reads
+
+
+# ------------------------------------------------------------------------------------------------------------ end to end
+SPHERE_R = 0.6
+
+
+def _sphere_view(c2w, W, focal):
+    y, x = np.meshgrid(np.arange(W), np.arange(W), indexing="ij")
+    cam = np.stack([(x - W / 2 + 0.5) / focal, -(y - W / 2 + 0.5) / focal, -np.ones_like(x, dtype=np.float64)], -1)
+    d = cam @ c2w[:3, :3].T
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o = c2w[:3, 3]
+    b = d @ o
+    disc = b * b - (o @ o - SPHERE_R ** 2)
+    hit = disc > 0
+    t = -b - np.sqrt(np.maximum(disc, 0))
+    p = o + t[..., None] * d
+    n = p / SPHERE_R
+    rgb = np.where(hit[..., None], (n + 1) / 2, 0.0)
+    a = hit.astype(np.float64)
+    return np.concatenate([rgb, a[..., None]], -1)
+
+
+def _write_scene(root, scene, n_views=40, W=128):
+    from PIL import Image
+    d = os.path.join(root, scene)
+    os.makedirs(os.path.join(d, "images"), exist_ok=True)
+    angle_x = 0.6911112070083618
+    focal = 0.5 * W / math.tan(0.5 * angle_x)
+    frames = []
+    rng = np.random.default_rng(0)
+    for i in range(n_views):
+        z = rng.uniform(-0.3, 0.9)
+        phi = rng.uniform(0, 2 * np.pi)
+        pos = np.array([math.sqrt(1 - z * z) * math.cos(phi), math.sqrt(1 - z * z) * math.sin(phi), z]) * 3.0
+        fwd = -pos / np.linalg.norm(pos)
+        right = np.cross(fwd, [0, 0, 1.0]); right /= np.linalg.norm(right)
+        up = np.cross(right, fwd)
+        c2w = np.eye(4)
+        c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = right, up, -fwd, pos
+        img = _sphere_view(c2w, W, focal)
+        Image.fromarray((img * 255).round().astype(np.uint8), "RGBA").save(os.path.join(d, "images", f"{i:03d}.png"))
+        frames.append({"file_path": f"images/{i:03d}", "transform_matrix": c2w.tolist()})
+    with open(os.path.join(d, "transforms.json"), "w") as fp:
+        json.dump({"camera_angle_x": angle_x, "frames": frames}, fp)
+
+
+# Calibrated on an MI355X: 35.39 dB held-out PSNR after 600 steps (one run); the floor leaves 5.4 dB of margin for the run-to-run spread of the
+# random rays, jitter and occupancy samples.
+PSNR_FLOOR = 30.0
+ITERS = 600
+
+
+def test_train_ngp_nerf_end_to_end(tmp_path):
+    """train_ngp_nerf.py on a normal-coloured sphere (40 views at 128 x 128, white background), then visibility.load_block and
+    eval_ngp_nerf.py on the written block: held-out PSNR above the floor and the extracted voxel_mask on the sphere's surface."""
+    _dev()
+    root = str(tmp_path)
+    _write_scene(root, "sphere")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    cmd = [sys.executable, os.path.join(ROOT, "train_ngp_nerf.py"), "--dataset", "objaverse", "--root_dir", root, "--scene", "sphere",
+           "--expname", "sphere", "--max_iterations", str(ITERS), "--n_validation", str(ITERS), "--n_checkpoint", str(ITERS)]
+    out = subprocess.run(["timeout", "-k", "10", "300"] + cmd, capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    m = re.findall(r"val psnr ([0-9.]+)", out.stdout)
+    assert m, out.stdout[-2000:]
+    psnr = float(m[-1])
+    print(f"E2E held-out PSNR after {ITERS} steps: {psnr:.2f} dB")
+    assert psnr >= PSNR_FLOOR, psnr
+    block = os.path.join(root, "out", "sphere", "model.pth")
+    assert os.path.exists(block)
+    from dreg_nerf_amd import visibility
+    field, grid, meta = visibility.load_block(block, torch.device("cuda:0"))
+    assert meta["camera_poses"].shape[0] == 38
+    # eval_ngp_nerf.py reads <root>/<dataset>/nerf_models/<scene>/block_k/model.pth
+    dst = os.path.join(root, "objaverse", "nerf_models", "sphere", "block_0")
+    os.makedirs(dst)
+    os.link(block, os.path.join(dst, "model.pth"))
+    out = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(ROOT, "eval_ngp_nerf.py"), "--root_dir", root, "--dataset",
+                          "objaverse", "--scene", "sphere"], capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    mask = torch.load(os.path.join(dst, "voxel_mask.pt"))
+    assert mask.numel() > 100
+    res = 128
+    ijk = torch.stack([mask // (res * res), (mask // res) % res, mask % res], -1).float()
+    centre = (ijk + 0.5) / res * 3.0 - 1.5
+    cell = 3.0 / res
+    r = centre.norm(dim=-1)
+    inside = (r <= SPHERE_R + 2 * cell).float().mean().item()
+    near = ((r - SPHERE_R).abs() <= 2 * cell).float().mean().item()
+    print(f"E2E voxel_mask: {mask.numel()} cells, {inside:.3f} within the ball + two cells, {near:.3f} within two cells of the surface")
+    # the kept cells are the object: (almost) nothing outside the sphere.  After this short run the density is solid inside the ball, so the
+    # surface visibility does not yet thin the set to the shell (reference blocks train 20,000 steps).
+    assert inside >= 0.9, inside
