@@ -140,7 +140,11 @@ class ProblemTable:
     segment of the shared row space.  self: q = kv = segment; cross: q = one segment, kv = the pair's other one."""
 
     def __init__(self, seg_lengths, device):
-        """seg_lengths: [(ns_0, nt_0), (ns_1, nt_1), ...] in row order."""
+        """seg_lengths: [(ns_0, nt_0), (ns_1, nt_1), ...] in row order.  Every segment holds at least one row: an attention problem
+        without keys has no softmax (the forward kernel would divide by a zero sum)."""
+        for ns, nt in seg_lengths:
+            if ns <= 0 or nt <= 0:
+                raise ValueError(f"ProblemTable: empty segment in {list(seg_lengths)}")
         starts, off = [], 0
         for ns, nt in seg_lengths:
             starts.append((off, ns, off + ns, nt))

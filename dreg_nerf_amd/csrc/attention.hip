@@ -359,10 +359,17 @@ __global__ __launch_bounds__(256, (D > 32 ? 2 : 1)) void attn_bwd_dq_kernel(Attn
                 for (int kk = 0; kk < D / 32; ++kk) s = mma(frag_row(sK, KRS, t * 16 + fr, kk * 32 + kg * 8, T()), qf[kk], s);
                 f32x4_t dp = (f32x4_t){0.f, 0.f, 0.f, 0.f};
                 if constexpr (!XYZ) dp = mma(frag_row(sV, VRS, t * 16 + fr, kg * 8, T()), dof, dp);
+                // Keys past Nk: their K (and V / xyz) rows are zero in LDS, but their p = exp2(0 * c2 - lse2) is +inf once the row's lse is
+                // below -88.7 (every score strongly negative), dS = inf * (0 - dvec) is inf or NaN and inf * 0 in the second product is NaN in
+                // dQ of a REAL query.  So they get p = 0 through a score of -inf, in the last tile only (a wave-uniform branch, as the forward).
+                if (k0 + 64 > pb.Nk) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (k0 + t * 16 + kg * 4 + r >= pb.Nk) s[r] = -INFINITY;
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int kr = t * 16 + kg * 4 + r;
-                    // keys past Nk need no mask: their K (and V / xyz) rows are zero in LDS, so whatever dS they get multiplies zero
                     const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -lse2));
                     float dpv = dp[r];
                     if constexpr (XYZ) {
@@ -477,7 +484,9 @@ __global__ __launch_bounds__(256, (D > 32 ? 2 : 1)) void attn_bwd_dkv_kernel(Att
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int ql = t * 16 + kg * 4 + r;
-                    // no masks: query rows past Nq are zero in LDS (Q, dO, lse, D), so their p multiplies zero; key columns past Nk are not stored
+                    // no masks.  Query rows past Nq are zero in LDS (Q, dO, lse, D): p = exp2(0) = 1 and dS = 1 * (0 - 0) = 0, both finite, multiply
+                    // zero rows of Q / dO.  Key columns past Nk (K = 0, so p = exp2(-lse2), possibly inf, and dS inf or NaN) are this LANE's column of
+                    // both second products (B operand column fr -> result column fr only) and are never stored: nothing non-finite reaches a real key.
                     const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -lq[r]));
                     float dpv = dp[r];
                     if constexpr (XYZ) {
