@@ -3,28 +3,10 @@
 //   * march_advance   — the lane's next lattice sample t_mid = t_min + (n + 1/2) dt that lies in an occupied cell of the binary grid
 //                       (nerfacc 0.3.5's marching rule; empty cells, and with the coarse bits empty 4^3 blocks, are skipped to their exit);
 //   * march_density   — the density of the wave's 64 samples: hash-grid gather per lane, then the 32 -> 64 -> 16 MLP on fp16 MFMA
-//                       through LDS (the arithmetic of ngp_density_kernel, csrc/ngp.hip);
+//                       through LDS (both stated in csrc/ngp_field.h, which the dense query of ngp.hip calls as well);
 //   * the caller's own use of sigma (labels there, compositing here).
 #pragma once
-#include "common.h"
-
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-struct NgpLevelsV {
-    uint32_t offset[16], size[16], res[16];
-    float scale[16];
-    uint32_t hashed[16];
-};
-
-// LDS row strides of the MLP tiles (bytes): 32 fp16 inputs / 64 fp16 hidden units per sample, padded against bank conflicts
-constexpr int MARCH_XRS = 32 * 2 + 16, MARCH_HRS = 64 * 2 + 16;
-
-__device__ __forceinline__ uint32_t vgrid_index(uint32_t x, uint32_t y, uint32_t z, uint32_t res, uint32_t size, uint32_t hashed) {
-    uint32_t idx = hashed ? (x ^ (y * 2654435761u) ^ (z * 805459861u)) : (x + y * res + z * res * res);
-    return idx % size;
-}
-
-__device__ __forceinline__ void march_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+#include "ngp_field.h"   // NgpLevels, NGP_XRS / NGP_HRS, wave_sync, the level gather and the density MLP
 
 // The occupancy grid a march walks: binary uint8 [rx,ry,rz] over the roi aabb, and optionally one bit per 4^3 block of it held in LDS (sCoarse).
 struct MarchGrid {
@@ -81,93 +63,34 @@ __device__ __forceinline__ bool march_advance(const MarchGrid& g, const float (&
     return false;
 }
 
-// The density MLP's weights as MFMA operands, held in registers for a whole launch: w1 fp16 [64][32], w2 fp16 [16][64].
-struct MarchDensityW { f16x8_t w1f[4], w2f[2]; };
-__device__ __forceinline__ void march_load_density_w(MarchDensityW& w, const _Float16* w1, const _Float16* w2, int lane)
-{
-    const int fr = lane & 15, kg = lane >> 4;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) w.w1f[cb] = *reinterpret_cast<const f16x8_t*>(w1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) w.w2f[kb] = *reinterpret_cast<const f16x8_t*>(w2 + fr * 64 + kb * 32 + kg * 8);
-}
-
 // Density of the wave's 64 samples (lane = sample; lanes without one, have == false, take a zero row).  Returns whether x lies strictly
 // inside the model aabb (outside: sigma = 0); sOut[lane] = fp16(h0), the density logit (sigma = exp(h0 - 1)).  FEAT: the 15 geometry
 // features h1..h15 are also left in LDS, fp16, in columns 16..30 of the sample's row of sX (the colour net's input row: render.hip).
-// sX: 64 rows of MARCH_XRS bytes, sH: 64 rows of MARCH_HRS bytes, sOut: 64 floats — all of this wave only.
-// The hidden layer's products are formed transposed (weights as the MFMA's first operand), so a lane holds four consecutive hidden units
-// of one sample and writes them with one 8-byte LDS store.
+// sX: 64 rows of NGP_XRS bytes, sH: 64 rows of NGP_HRS bytes (apart from sX), sOut: 64 floats — all of this wave only.
 template <bool FEAT>
-__device__ __forceinline__ bool march_density(bool have, const float (&x)[3], const float* model, const NgpLevelsV& lv, const _Float16* table,
-                                              const MarchDensityW& w, char* sX, char* sH, float* sOut, int lane)
+__device__ __forceinline__ bool march_density(bool have, const float (&x)[3], const float* model, const NgpLevels& lv, const _Float16* table,
+                                              const NgpDensityW& w, char* sX, char* sH, float* sOut, int lane)
 {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
     const int fr = lane & 15, kg = lane >> 4;
     float u[3];
-    bool inside_m = have;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        u[k] = (x[k] - model[k]) / (model[3 + k] - model[k]);
-        inside_m = inside_m && u[k] > 0.f && u[k] < 1.f;
-        u[k] = fminf(fmaxf(u[k], 0.f), 1.f);
-    }
+    const bool inside_m = ngp_unit_cube(x, model, model + 3, 0, u) && have;
 #pragma unroll 2
     for (int l = 0; l < 16; ++l) {
         float f0 = 0.f, f1 = 0.f;
-        if (have) {
-            const float sc = lv.scale[l];
-            const uint32_t res = lv.res[l], size = lv.size[l], hashed = lv.hashed[l];
-            const _Float16* tl = table + (size_t)lv.offset[l] * 2;
-            float wt3[3];
-            uint32_t g[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { const float pos = u[k] * sc + 0.5f; const float fl = floorf(pos); g[k] = (uint32_t)fl; wt3[k] = pos - fl; }
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const uint32_t cx = g[0] + (corner & 1), cy = g[1] + ((corner >> 1) & 1), cz = g[2] + ((corner >> 2) & 1);
-                const float wt = ((corner & 1) ? wt3[0] : 1.f - wt3[0]) * ((corner & 2) ? wt3[1] : 1.f - wt3[1]) * ((corner & 4) ? wt3[2] : 1.f - wt3[2]);
-                union { uint32_t u32; _Float16 h[2]; } cv;
-                cv.u32 = *reinterpret_cast<const uint32_t*>(tl + (size_t)vgrid_index(cx, cy, cz, res, size, hashed) * 2);
-                f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
-            }
-        }
-        _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS);
+        if (have) ngp_level_features(table, lv, l, u, f0, f1);
+        _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * NGP_XRS);
         xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
     }
-    march_wave_sync();
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) {
-        const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * MARCH_XRS + kg * 16);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.w1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    }
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const f32x4_t v = acc[rb][cb];       // hidden units cb*16 + kg*4 .. +3 of sample rb*16 + fr
-            const f16x4_t h = {(_Float16)fmaxf(v[0], 0.f), (_Float16)fmaxf(v[1], 0.f), (_Float16)fmaxf(v[2], 0.f), (_Float16)fmaxf(v[3], 0.f)};
-            *reinterpret_cast<f16x4_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2) = h;
-        }
-    march_wave_sync();
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) {
-        f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-            ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2), w.w2f[kb], ov, 0, 0, 0);
-        // ov[r] = output fr of sample rb*16 + kg*4 + r
+    ngp_density_mlp(w, sX, sH, lane, [&](int rb, const f32x4_t& ov) {      // ov[r] = output fr of sample rb*16 + kg*4 + r
         if (fr == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) sOut[rb * 16 + kg * 4 + r] = (float)(_Float16)ov[r];
         } else if (FEAT) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) reinterpret_cast<_Float16*>(sX + (rb * 16 + kg * 4 + r) * MARCH_XRS)[15 + fr] = (_Float16)ov[r];
+            for (int r = 0; r < 4; ++r) reinterpret_cast<_Float16*>(sX + (rb * 16 + kg * 4 + r) * NGP_XRS)[15 + fr] = (_Float16)ov[r];
         }
-    }
-    march_wave_sync();
+    });
+    wave_sync();
     return inside_m;
 }
 
@@ -224,10 +147,10 @@ __device__ __forceinline__ void march_color(char* sX, char* sH1, char* sH2, floa
 {
     typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
     const int fr = lane & 15, kg = lane >> 4;
-    march_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
-        const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * MARCH_XRS + kg * 16);
+        const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * NGP_XRS + kg * 16);
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             const f32x4_t v = __builtin_amdgcn_mfma_f32_16x16x32_f16(cw1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -235,16 +158,16 @@ __device__ __forceinline__ void march_color(char* sX, char* sH1, char* sH2, floa
             f16x2_t p = {(_Float16)v[0], (_Float16)v[1]}, q = {(_Float16)v[2], (_Float16)v[3]};
             p = __builtin_elementwise_max(p, z);
             q = __builtin_elementwise_max(q, z);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(sH1 + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(sH1 + (rb * 16 + fr) * NGP_HRS + (cb * 16 + kg * 4) * 2);
             dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
         }
     }
-    march_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
         f16x8_t af[2];
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) af[kb] = *reinterpret_cast<const f16x8_t*>(sH1 + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2);
+        for (int kb = 0; kb < 2; ++kb) af[kb] = *reinterpret_cast<const f16x8_t*>(sH1 + (rb * 16 + fr) * NGP_HRS + (kb * 32 + kg * 8) * 2);
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             f32x4_t h = (f32x4_t){0.f, 0.f, 0.f, 0.f};
@@ -255,23 +178,23 @@ __device__ __forceinline__ void march_color(char* sX, char* sH1, char* sH2, floa
             f16x2_t p = {(_Float16)h[0], (_Float16)h[1]}, q = {(_Float16)h[2], (_Float16)h[3]};
             p = __builtin_elementwise_max(p, z);
             q = __builtin_elementwise_max(q, z);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(sH2 + (rb * 16 + fr) * MARCH_HRS + (cb * 16 + kg * 4) * 2);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(sH2 + (rb * 16 + fr) * NGP_HRS + (cb * 16 + kg * 4) * 2);
             dst[0] = __builtin_bit_cast(uint32_t, p); dst[1] = __builtin_bit_cast(uint32_t, q);
         }
     }
-    march_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
         f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
-            ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH2 + (rb * 16 + fr) * MARCH_HRS + (kb * 32 + kg * 8) * 2), cw3f[kb], ov, 0, 0, 0);
+            ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH2 + (rb * 16 + fr) * NGP_HRS + (kb * 32 + kg * 8) * 2), cw3f[kb], ov, 0, 0, 0);
         if (fr < 4) {        // channel fr of samples rb*16 + kg*4 + r (channel 3 is padding: written, never read)
 #pragma unroll
             for (int r = 0; r < 4; ++r) sO[(rb * 16 + kg * 4 + r) * 4 + fr] = ov[r];
         }
     }
-    march_wave_sync();
+    wave_sync();
 }
 
 // fp16 colour channel of a pre-activation (the forward's sigmoid, rounded as tcnn's fp16 output)

@@ -10,41 +10,7 @@
 // interpolation in fp32 rounded to fp16, layer inputs fp16, accumulation fp32 (tcnn accumulates in fp16 — unpinned).
 // The 18 viewing directions are constants of the caller, so the SH half of the colour net's first layer collapses to one
 // bias vector per direction (c_k = W1[:, :16] sh_k, computed by the caller) and the geometry half is computed once per point.
-#include "common.h"
-
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-struct NgpLevels {
-    uint32_t offset[16];   // first entry of the level (entries of 2 features)
-    uint32_t size[16];     // entries in the level
-    uint32_t res[16];
-    float scale[16];
-    uint32_t hashed[16];
-};
-
-__device__ __forceinline__ uint32_t grid_index(uint32_t x, uint32_t y, uint32_t z, uint32_t res, uint32_t size, uint32_t hashed) {
-    uint32_t idx = hashed ? (x ^ (y * 2654435761u) ^ (z * 805459861u)) : (x + y * res + z * res * res);
-    return idx % size;
-}
-
-__device__ __forceinline__ f16x8_t ldsfrag(const char* base, int rs, int row, int k0) {
-    return *reinterpret_cast<const f16x8_t*>(base + row * rs + k0 * 2);
-}
-
-// Every wave owns its 64 points and its own slice of LDS (sX / sH of wave w): what one layer writes is read back by the SAME wave.  LDS
-// instructions of a wave execute in issue order, so no workgroup barrier is needed between the layers — only the compiler must not
-// move the reads above the writes.  (Six __syncthreads per direction kept the four waves of a workgroup in lockstep.)
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
-// Hidden activations go back to LDS between the layers.  The products are formed TRANSPOSED (weights as the MFMA's first operand), so a
-// lane holds four consecutive hidden units of one point: one 8-byte LDS write of four fp16 instead of four 2-byte writes (the layers
-// are 16-64 MFMAs each; 64 scalar LDS writes per lane and layer were most of the kernel).  Same products, same sums: bit-identical.
-__device__ __forceinline__ void store_relu4(char* sH, int row_stride, int point, int hidden, const f32x4_t& v, float b0 = 0.f, float b1 = 0.f, float b2 = 0.f, float b3 = 0.f)
-{
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-    const f16x4_t h = {(_Float16)fmaxf(v[0] + b0, 0.f), (_Float16)fmaxf(v[1] + b1, 0.f), (_Float16)fmaxf(v[2] + b2, 0.f), (_Float16)fmaxf(v[3] + b3, 0.f)};
-    *reinterpret_cast<f16x4_t*>(sH + point * row_stride + hidden * 2) = h;
-}
+#include "ngp_field.h"    // NgpLevels, the hash-grid level gather, the density MLP, wave_sync, store_relu4: shared with the ray marchers (march.h)
 
 // The same with the ReLU on the packed-half VALU: round the four sums to fp16 first (round-to-nearest, as the plain cast), then ONE
 // v_pk_max_f16 per pair — relu(rn(x)) == rn(relu(x)), so the stored bits are those of store_relu4.  (The library is built without
@@ -65,60 +31,15 @@ __device__ __forceinline__ void store_relu4_pk(char* sH, int row_stride, int poi
 // x world [Np,3] fp32 -> density fp32 [Np] (= exp(h0 - 1) * inside), raw fp16 [Np,16] (h0 | 15 geometry features)
 // one wave per workgroup: the waves are independent (no workgroup barrier), and 5,081 small workgroups for a 325 k-point block fill
 // the chip evenly where 1,270 four-wave ones left a quarter-full second round
-// unit-cube coordinates of point p (clamped) and whether it lies strictly inside (ngp.py:157-167)
+// unit-cube coordinates of point p (clamped) and whether it lies strictly inside; a slot past the last point: u = 0, outside
 __device__ __forceinline__ bool ngp_unit_coords(const float* __restrict__ x, int p, int Np, float lo0, float lo1, float lo2, float hi0, float hi1, float hi2,
                                                 int contract, float (&u)[3])
 {
     u[0] = u[1] = u[2] = 0.f;
-    bool inside = false;
-    if (p < Np) {
-        const float lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
-        inside = true;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) u[c] = (x[(size_t)p * 3 + c] - lo[c]) / (hi[c] - lo[c]);
-        if (contract) {
-            // contract_to_unisphere (conerf/radiance_fields/ngp.py:41-63): the aabb maps to [-1,1]^3, points of norm > 1 are pulled
-            // onto the shell (2 - 1/|x|) x/|x| of radius < 2, and [-2,2]^3 maps to [0,1]^3
-            float v[3], m2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { v[c] = u[c] * 2.f - 1.f; m2 += v[c] * v[c]; }
-            const float mag = sqrtf(m2);
-            if (mag > 1.f) {
-                const float sc = (2.f - 1.f / mag) / mag;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] *= sc;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = v[c] / 4.f + 0.5f;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            inside = inside && (u[c] > 0.f) && (u[c] < 1.f);
-            u[c] = fminf(fmaxf(u[c], 0.f), 1.f);
-        }
-    }
-    return inside;
-}
-// trilinear interpolation of level l's two features at unit coordinates u (8 corner gathers of 4 bytes)
-__device__ __forceinline__ void ngp_level_features(const _Float16* __restrict__ table, const NgpLevels& lv, int l, const float (&u)[3], float& f0, float& f1)
-{
-    const float sc = lv.scale[l];
-    const uint32_t res = lv.res[l], size = lv.size[l], hashed = lv.hashed[l];
-    const _Float16* tl = table + (size_t)lv.offset[l] * 2;
-    float pos[3], w[3];
-    uint32_t g[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { pos[c] = u[c] * sc + 0.5f; const float fl = floorf(pos[c]); g[c] = (uint32_t)fl; w[c] = pos[c] - fl; }
-    f0 = 0.f; f1 = 0.f;
-#pragma unroll
-    for (int corner = 0; corner < 8; ++corner) {
-        const uint32_t cx = g[0] + (corner & 1), cy = g[1] + ((corner >> 1) & 1), cz = g[2] + ((corner >> 2) & 1);
-        const float wt = ((corner & 1) ? w[0] : 1.f - w[0]) * ((corner & 2) ? w[1] : 1.f - w[1]) * ((corner & 4) ? w[2] : 1.f - w[2]);
-        const uint32_t idx = grid_index(cx, cy, cz, res, size, hashed);
-        const uint32_t pr = *reinterpret_cast<const uint32_t*>(tl + (size_t)idx * 2);
-        union { uint32_t u32; _Float16 h[2]; } cv; cv.u32 = pr;
-        f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
-    }
+    if (p >= Np) return false;
+    const float lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
+    const float xp[3] = {x[(size_t)p * 3], x[(size_t)p * 3 + 1], x[(size_t)p * 3 + 2]};
+    return ngp_unit_cube(xp, lo, hi, contract, u);
 }
 
 // Hash-grid encoding with the table held in L2: the 16 levels are 25 MB (fits the Infinity Cache, not one XCD's 4 MB L2), and a wave
@@ -163,7 +84,7 @@ __global__ __launch_bounds__(64) void ngp_density_kernel(const float* __restrict
                                                           int contract, const _Float16* __restrict__ feat = nullptr, const int* __restrict__ order = nullptr,
                                                           int x_in_slot_order = 0, NgpKeepEpi ke = NgpKeepEpi{})
 {
-    constexpr int XRS = 32 * 2 + 16, HRS = 64 * 2 + 16;
+    constexpr int XRS = NGP_XRS, HRS = NGP_HRS;
     // per wave: ONE 64 x 64 fp16 tile (the encoded input X lives in its first 5 KB until the first layer has read it) + 64 flags:
     // 9.5 KB per wave, 38 KB per workgroup -> four workgroups per CU (the gathers of the 16 levels are latency: occupancy hides them)
     __shared__ __attribute__((aligned(16))) char smem[64 * HRS + 64 * 4 + 64 * 4];
@@ -197,33 +118,11 @@ __global__ __launch_bounds__(64) void ngp_density_kernel(const float* __restrict
             xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
         }
     }
-    wave_sync();
+    // (sX lies inside sH: allowed by ngp_density_mlp, the epilogue below does not touch sX)
+    NgpDensityW dw;
+    ngp_load_density_w(dw, w1, w2, lane);
     const int fr = lane & 15, kg = lane >> 4;
-    f32x4_t acc[4][4];
-    {
-        f16x8_t bf[4];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) bf[cb] = *reinterpret_cast<const f16x8_t*>(w1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            const f16x8_t af = ldsfrag(sX, XRS, rb * 16 + fr, kg * 8);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) store_relu4(sH, HRS, rb * 16 + fr, cb * 16 + kg * 4, acc[rb][cb]);
-    wave_sync();
-    f16x8_t w2f[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) w2f[kb] = *reinterpret_cast<const f16x8_t*>(w2 + fr * 64 + kb * 32 + kg * 8);
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb) {
-        f32x4_t o = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) o = __builtin_amdgcn_mfma_f32_16x16x32_f16(ldsfrag(sH, HRS, rb * 16 + fr, kb * 32 + kg * 8), w2f[kb], o, 0, 0, 0);
+    ngp_density_mlp(dw, sX, sH, lane, [&](int rb, const f32x4_t& o) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = rb * 16 + kg * 4 + r;
@@ -242,7 +141,7 @@ __global__ __launch_bounds__(64) void ngp_density_kernel(const float* __restrict
                 }
             }
         }
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ colour, 18 directions
@@ -252,7 +151,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                                                       const _Float16* __restrict__ w3, const float* __restrict__ dirbias,
                                                       float* __restrict__ rgb, int ndir, int Np, const float* __restrict__ dirs = nullptr)
 {
-    constexpr int XRS = 32 * 2 + 16, HRS = 64 * 2 + 16;
+    constexpr int XRS = NGP_XRS, HRS = NGP_HRS;
     // per wave ONE 64 x 64 fp16 tile: X (prologue only) aliases it, and the second layer overwrites the first layer's activations in
     // place — a 16-row block is read into registers in full before its outputs are written.  9 KB per wave instead of 23.5 KB: four
     // workgroups per CU instead of one (one wave per SIMD had nothing to hide the LDS round trips and MFMA dependency chains with).
@@ -386,7 +285,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const _Float16* __restrict__ raw, const _Float16* __restrict__ w1, const _Float16* __restrict__ w2, const _Float16* __restrict__ w3,
     const uint32_t* __restrict__ biaspk, float* __restrict__ rgb, int ndir, int Np)
 {
-    constexpr int XRS = 32 * 2 + 16, HRS = 64 * 2 + 16;
+    constexpr int XRS = NGP_XRS, HRS = NGP_HRS;
     __shared__ __attribute__((aligned(16))) char sH[16 * HRS];      // one 16 x 64 fp16 tile (X aliases its first rows)
     __shared__ __attribute__((aligned(16))) float sO[16 * 4];
     const int lane = threadIdx.x & 63;
@@ -653,7 +552,7 @@ int dreg_ngp_density_fwd(const float* x, const void* table, const void* w1, cons
 {
     if (Np == 0) return DREG_OK;
     NgpLevels lv;
-    for (int l = 0; l < 16; ++l) { lv.offset[l] = offset[l]; lv.size[l] = size[l]; lv.res[l] = res[l]; lv.scale[l] = scale[l]; lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(lv, offset, size, res, scale, hashed);
     ngp_density_launch(x, table, w1, w2, density, raw, lv, aabb, Np, 0, stream);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
@@ -666,7 +565,7 @@ int dreg_ngp_density_fwd_contract(const float* x, const void* table, const void*
 {
     if (Np == 0) return DREG_OK;
     NgpLevels lv;
-    for (int l = 0; l < 16; ++l) { lv.offset[l] = offset[l]; lv.size[l] = size[l]; lv.res[l] = res[l]; lv.scale[l] = scale[l]; lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(lv, offset, size, res, scale, hashed);
     ngp_density_launch(x, table, w1, w2, density, raw, lv, aabb, Np, contract, stream);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
@@ -683,7 +582,7 @@ int dreg_ngp_density_fwd_ws(const float* x, const void* table, const void* w1, c
 {
     if (Np == 0) return DREG_OK;
     NgpLevels lv;
-    for (int l = 0; l < 16; ++l) { lv.offset[l] = offset[l]; lv.size[l] = size[l]; lv.res[l] = res[l]; lv.scale[l] = scale[l]; lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(lv, offset, size, res, scale, hashed);
     if (g_ngp_xcd_levels && workspace && workspace_bytes >= dreg_ngp_density_workspace_bytes(Np)) ngp_density_launch_xcd(x, table, w1, w2, density, raw, lv, aabb, Np, contract, workspace, stream, order, order ? x_in_slot_order : 0);
     else ngp_density_launch(x, table, w1, w2, density, raw, lv, aabb, Np, contract, stream, order, order ? x_in_slot_order : 0);
     DREG_LAUNCH_CHECK();
@@ -1044,7 +943,7 @@ int dreg_ngp_density_keep_fwd_ws(const float* x, const void* table, const void* 
     if (Np == 0) return DREG_OK;
     if (!alpha || !keep) return DREG_EINVAL;
     NgpLevels lv;
-    for (int l = 0; l < 16; ++l) { lv.offset[l] = offset[l]; lv.size[l] = size[l]; lv.res[l] = res[l]; lv.scale[l] = scale[l]; lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(lv, offset, size, res, scale, hashed);
     NgpKeepEpi ke{alpha, keep, delta, threshold};
     if (g_ngp_xcd_levels && workspace && workspace_bytes >= dreg_ngp_density_workspace_bytes(Np))
         ngp_density_launch_xcd(x, table, w1, w2, density, raw, lv, aabb, Np, contract, workspace, stream, order, order ? x_in_slot_order : 0, ke);

@@ -1,0 +1,158 @@
+// The density field of a NeRF block (Instant-NGP), stated once for every kernel that evaluates it (gfx950, wave64): the 16-level hash-grid
+// encoding of a point (NGPradianceField.query_density, conerf/radiance_fields/ngp.py:148-176: HashGrid L=16 F=2) and the 32 -> 64 -> 16
+// density MLP on fp16 MFMA (16x16x32) through LDS.  The dense query (ngp.hip), the ray marchers (march.h: visibility.hip, render.hip) and
+// the training backward (render_train.hip), which re-marches every ray, must agree bit for bit: they all call the functions below.
+// Table and weights are fp16, trilinear interpolation in fp32 rounded to fp16, layer inputs fp16, accumulation fp32.
+#pragma once
+#include "common.h"
+
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+
+// LDS row strides of the MLP tiles (bytes): 32 fp16 inputs / 64 fp16 hidden units per sample, padded against bank conflicts
+constexpr int NGP_XRS = 32 * 2 + 16, NGP_HRS = 64 * 2 + 16;
+
+struct NgpLevels {
+    uint32_t offset[16];   // first entry of the level (entries of 2 features)
+    uint32_t size[16];     // entries in the level
+    uint32_t res[16];
+    float scale[16];
+    uint32_t hashed[16];
+};
+// from the five 16-entry host arrays of the C ABI (as produced by dreg_ngp_level_table)
+static inline void ngp_fill_levels(NgpLevels& lv, const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed)
+{
+    for (int l = 0; l < 16; ++l) { lv.offset[l] = offset[l]; lv.size[l] = size[l]; lv.res[l] = res[l]; lv.scale[l] = scale[l]; lv.hashed[l] = hashed[l]; }
+}
+
+__device__ __forceinline__ uint32_t grid_index(uint32_t x, uint32_t y, uint32_t z, uint32_t res, uint32_t size, uint32_t hashed) {
+    uint32_t idx = hashed ? (x ^ (y * 2654435761u) ^ (z * 805459861u)) : (x + y * res + z * res * res);
+    return idx % size;
+}
+
+__device__ __forceinline__ f16x8_t ldsfrag(const char* base, int rs, int row, int k0) {
+    return *reinterpret_cast<const f16x8_t*>(base + row * rs + k0 * 2);
+}
+
+// Every wave owns its 64 points and its own slice of LDS (sX / sH of wave w): what one layer writes is read back by the SAME wave.  LDS
+// instructions of a wave execute in issue order, so no workgroup barrier is needed between the layers — only the compiler must not
+// move the reads above the writes.  (Six __syncthreads per direction kept the four waves of a workgroup in lockstep.)
+__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+// Hidden activations go back to LDS between the layers.  The products are formed TRANSPOSED (weights as the MFMA's first operand), so a
+// lane holds four consecutive hidden units of one point: one 8-byte LDS write of four fp16 instead of four 2-byte writes (the layers
+// are 16-64 MFMAs each; 64 scalar LDS writes per lane and layer were most of the kernel).  Same products, same sums: bit-identical.
+__device__ __forceinline__ void store_relu4(char* sH, int row_stride, int point, int hidden, const f32x4_t& v)
+{
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+    const f16x4_t h = {(_Float16)fmaxf(v[0], 0.f), (_Float16)fmaxf(v[1], 0.f), (_Float16)fmaxf(v[2], 0.f), (_Float16)fmaxf(v[3], 0.f)};
+    *reinterpret_cast<f16x4_t*>(sH + point * row_stride + hidden * 2) = h;
+}
+
+// ------------------------------------------------------------------------------------------------ unit coordinates
+// Unit-cube coordinates u (clamped to [0,1]) of the world position x in the aabb (lo, hi), and whether x lies strictly inside
+// (ngp.py:157-167; outside, the callers set the density to 0).
+__device__ __forceinline__ bool ngp_unit_cube(const float (&x)[3], const float* lo, const float* hi, int contract, float (&u)[3])
+{
+    bool inside = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = (x[c] - lo[c]) / (hi[c] - lo[c]);
+    if (contract) {
+        // contract_to_unisphere (conerf/radiance_fields/ngp.py:41-63): the aabb maps to [-1,1]^3, points of norm > 1 are pulled
+        // onto the shell (2 - 1/|x|) x/|x| of radius < 2, and [-2,2]^3 maps to [0,1]^3
+        float v[3], m2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { v[c] = u[c] * 2.f - 1.f; m2 += v[c] * v[c]; }
+        const float mag = sqrtf(m2);
+        if (mag > 1.f) {
+            const float sc = (2.f - 1.f / mag) / mag;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] *= sc;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u[c] = v[c] / 4.f + 0.5f;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        inside = inside && (u[c] > 0.f) && (u[c] < 1.f);
+        u[c] = fminf(fmaxf(u[c], 0.f), 1.f);
+    }
+    return inside;
+}
+
+// ------------------------------------------------------------------------------------------------ hash-grid level
+// The 8 corners of level l around unit coordinates u: hook(e, wt) is called per corner with e = the corner's first fp16 element within
+// the level (2 * entry: add 2 * lv.offset[l] for the whole table) and its trilinear weight.  hook is a lambda, inlined: no indirect call.
+template <typename Hook>
+__device__ __forceinline__ void ngp_level_corners(const NgpLevels& lv, int l, const float (&u)[3], Hook&& hook)
+{
+    const float sc = lv.scale[l];
+    const uint32_t res = lv.res[l], size = lv.size[l], hashed = lv.hashed[l];
+    float pos[3], w[3];
+    uint32_t g[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { pos[c] = u[c] * sc + 0.5f; const float fl = floorf(pos[c]); g[c] = (uint32_t)fl; w[c] = pos[c] - fl; }
+#pragma unroll
+    for (int corner = 0; corner < 8; ++corner) {
+        const uint32_t cx = g[0] + (corner & 1), cy = g[1] + ((corner >> 1) & 1), cz = g[2] + ((corner >> 2) & 1);
+        const float wt = ((corner & 1) ? w[0] : 1.f - w[0]) * ((corner & 2) ? w[1] : 1.f - w[1]) * ((corner & 4) ? w[2] : 1.f - w[2]);
+        hook((size_t)grid_index(cx, cy, cz, res, size, hashed) * 2, wt);
+    }
+}
+// one corner's share of the level's two features: a 4-byte gather of the fp16 pair at tl + e
+__device__ __forceinline__ void ngp_corner_accumulate(const _Float16* tl, size_t e, float wt, float& f0, float& f1)
+{
+    union { uint32_t u32; _Float16 h[2]; } cv;
+    cv.u32 = *reinterpret_cast<const uint32_t*>(tl + e);
+    f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
+}
+// trilinear interpolation of level l's two features at unit coordinates u (8 corner gathers of 4 bytes)
+__device__ __forceinline__ void ngp_level_features(const _Float16* __restrict__ table, const NgpLevels& lv, int l, const float (&u)[3], float& f0, float& f1)
+{
+    const _Float16* tl = table + (size_t)lv.offset[l] * 2;
+    f0 = 0.f; f1 = 0.f;
+    ngp_level_corners(lv, l, u, [&](size_t e, float wt) { ngp_corner_accumulate(tl, e, wt, f0, f1); });
+}
+
+// ------------------------------------------------------------------------------------------------ density MLP
+// The density MLP's weights as MFMA operands, held in registers: w1 fp16 [64][32], w2 fp16 [16][64].
+struct NgpDensityW { f16x8_t w1f[4], w2f[2]; };
+__device__ __forceinline__ void ngp_load_density_w(NgpDensityW& w, const _Float16* w1, const _Float16* w2, int lane)
+{
+    const int fr = lane & 15, kg = lane >> 4;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) w.w1f[cb] = *reinterpret_cast<const f16x8_t*>(w1 + (cb * 16 + fr) * 32 + kg * 8);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) w.w2f[kb] = *reinterpret_cast<const f16x8_t*>(w2 + fr * 64 + kb * 32 + kg * 8);
+}
+
+// The 32 -> 64 -> 16 net over the wave's 64 samples: input rows in sX (64 rows of NGP_XRS bytes, 32 fp16 each, written by this wave
+// before the call) -> fp32 sums -> ReLU, fp16 rows in sH (64 rows of NGP_HRS bytes) -> second layer.  epi(rb, ov) receives, for each
+// block rb of 16 samples, ov[r] = output (lane & 15) of sample rb*16 + (lane >> 4)*4 + r, fp32.
+// Aliasing: sX may lie INSIDE sH (ngp_density_kernel keeps one tile per wave) — every first-layer sum is formed before the first store to
+// sH — but then epi must not write to sX.  An epi that writes sX (march_density<FEAT>) needs sX and sH apart.  Buffers that epi fills for
+// the caller need the caller's wave_sync() before they are read.
+template <typename Epi>
+__device__ __forceinline__ void ngp_density_mlp(const NgpDensityW& w, const char* sX, char* sH, int lane, Epi&& epi)
+{
+    const int fr = lane & 15, kg = lane >> 4;
+    wave_sync();
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        const f16x8_t af = ldsfrag(sX, NGP_XRS, rb * 16 + fr, kg * 8);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.w1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    }
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) store_relu4(sH, NGP_HRS, rb * 16 + fr, cb * 16 + kg * 4, acc[rb][cb]);   // hidden units cb*16 + kg*4 .. +3 of sample rb*16 + fr
+    wave_sync();
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(ldsfrag(sH, NGP_HRS, rb * 16 + fr, kb * 32 + kg * 8), w.w2f[kb], ov, 0, 0, 0);
+        epi(rb, ov);
+    }
+}

@@ -29,7 +29,7 @@ struct RenderArgs {
     long n_rays;
     const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
     const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]
-    NgpLevelsV lv;
+    NgpLevels lv;
     const uint8_t* binary;
     const uint32_t* coarse;     // optional coarse bits (dreg_occupancy_coarse_bits), <= 32,768 bits; null = none
     int rx, ry, rz, cx, cy, cz;
@@ -55,8 +55,8 @@ __device__ __forceinline__ void render_write(const RenderArgs& a, long ray, cons
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ngp_render_kernel(RenderArgs a)
 {
-    __shared__ __attribute__((aligned(16))) char sX[64 * MARCH_XRS];
-    __shared__ __attribute__((aligned(16))) char sH[64 * MARCH_HRS];
+    __shared__ __attribute__((aligned(16))) char sX[64 * NGP_XRS];
+    __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];
     __shared__ float sOut[64];
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
     __shared__ uint32_t sCoarse[1024];
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
     g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
-    MarchDensityW dw;
-    march_load_density_w(dw, a.w1, a.w2, lane);
+    NgpDensityW dw;
+    ngp_load_density_w(dw, a.w1, a.w2, lane);
     f16x8_t cw1f[4], cw3f[2];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
@@ -147,10 +147,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             if (surv) {
                 w = alpha * T_s;
                 T_s *= (1.f - alpha);
-                uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * MARCH_XRS);
+                uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
-                reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS)[31] = (_Float16)1.f;
+                reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
             }
         }
         if (__any(surv)) {
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             }
         }
         if (have && T_all < a.eps) { active = false; render_write(a, ray, acc, opac, dep); }    // transmittance below early_stop_eps: the ray ends
-        march_wave_sync();
+        wave_sync();
     }
     // the survivors this wave composited: one atomic per wave
     unsigned long long tot = my_samples;
@@ -194,7 +194,7 @@ static int render_launch(const float* origins, const float* viewdirs, const floa
     a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
     a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
     a.cw1 = (const _Float16*)cw1; a.cw2 = (const _Float16*)cw2; a.cw3 = (const _Float16*)cw3;
-    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
     for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
     for (int k = 0; k < 3; ++k) a.bkgd[k] = bkgd[k];
     a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;

@@ -32,7 +32,7 @@ struct RenderBwdArgs {
     long n_rays;
     const _Float16 *table, *w1, *w2, *cw1, *cw2, *cw3;
     const float* wf;                   // fp32 copies of the five weight matrices, slab layout
-    NgpLevelsV lv;
+    NgpLevels lv;
     const uint8_t* binary;
     const uint32_t* coarse;
     int rx, ry, rz, cx, cy, cz;
@@ -80,10 +80,10 @@ __device__ __forceinline__ void bwd_outer(float* slab, int ld, const float* sA, 
 
 __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 {
-    __shared__ __attribute__((aligned(16))) char sX[64 * MARCH_XRS];     // density input, then the colour input rows, then the encoding again
-    __shared__ __attribute__((aligned(16))) char sH[64 * MARCH_HRS];     // density hidden layer
-    __shared__ __attribute__((aligned(16))) char sH1[64 * MARCH_HRS];    // colour hidden layers
-    __shared__ __attribute__((aligned(16))) char sH2[64 * MARCH_HRS];
+    __shared__ __attribute__((aligned(16))) char sX[64 * NGP_XRS];     // density input, then the colour input rows, then the encoding again
+    __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];     // density hidden layer
+    __shared__ __attribute__((aligned(16))) char sH1[64 * NGP_HRS];    // colour hidden layers
+    __shared__ __attribute__((aligned(16))) char sH2[64 * NGP_HRS];
     __shared__ __attribute__((aligned(16))) float sA[64 * BWD_AS];
     __shared__ float sOut[64], sLive[64];
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
     g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
-    MarchDensityW dw;
-    march_load_density_w(dw, a.w1, a.w2, lane);
+    NgpDensityW dw;
+    ngp_load_density_w(dw, a.w1, a.w2, lane);
     f16x8_t cw1f[4], cw3f[2];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
@@ -180,10 +180,10 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                 if (surv) {
                     w = alpha * T_s;
                     T_s *= (1.f - alpha);                                 // = T_{k+1}
-                    uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * MARCH_XRS);
+                    uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
-                    reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS)[31] = (_Float16)1.f;
+                    reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
                 }
             }
             if (__any(surv)) {
@@ -206,22 +206,22 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                 // colour W3 (rows 0..2 of 16): dW3[c][i] += dO[c] h2[i]
 #pragma unroll
                 for (int c = 0; c < 16; ++c) rowA[c] = c < 3 ? dO[c] : 0.f;
-                march_wave_sync();
-                bwd_outer<1, 4>(slab + BWD_OFF_C3, 64, sA, sH2, MARCH_HRS, sLive, lane);
-                const _Float16* h2 = reinterpret_cast<const _Float16*>(sH2 + lane * MARCH_HRS);
-                const _Float16* h1 = reinterpret_cast<const _Float16*>(sH1 + lane * MARCH_HRS);
+                wave_sync();
+                bwd_outer<1, 4>(slab + BWD_OFF_C3, 64, sA, sH2, NGP_HRS, sLive, lane);
+                const _Float16* h2 = reinterpret_cast<const _Float16*>(sH2 + lane * NGP_HRS);
+                const _Float16* h1 = reinterpret_cast<const _Float16*>(sH1 + lane * NGP_HRS);
                 float d2[64];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) {
                     const float s = wc3[i] * dO[0] + wc3[64 + i] * dO[1] + wc3[128 + i] * dO[2];
                     d2[i] = (float)h2[i] > 0.f ? s : 0.f;
                 }
-                march_wave_sync();
+                wave_sync();
                 // colour W2: dW2[j][i] += d2[j] h1[i]
 #pragma unroll
                 for (int j = 0; j < 64; ++j) rowA[j] = d2[j];
-                march_wave_sync();
-                bwd_outer<4, 4>(slab + BWD_OFF_C2, 64, sA, sH1, MARCH_HRS, sLive, lane);
+                wave_sync();
+                bwd_outer<4, 4>(slab + BWD_OFF_C2, 64, sA, sH1, NGP_HRS, sLive, lane);
                 float d1[64];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) d1[i] = 0.f;
@@ -233,12 +233,12 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                 }
 #pragma unroll
                 for (int i = 0; i < 64; ++i) d1[i] = (float)h1[i] > 0.f ? d1[i] : 0.f;
-                march_wave_sync();
+                wave_sync();
                 // colour W1: dW1[i][k] += d1[i] x[k]; the 15 feature inputs (columns 16..30) carry the gradient on
 #pragma unroll
                 for (int i = 0; i < 64; ++i) rowA[i] = d1[i];
-                march_wave_sync();
-                bwd_outer<4, 2>(slab + BWD_OFF_C1, 32, sA, sX, MARCH_XRS, sLive, lane);
+                wave_sync();
+                bwd_outer<4, 2>(slab + BWD_OFF_C1, 32, sA, sX, NGP_XRS, sLive, lane);
                 float dout[16];
                 dout[0] = dh0;
 #pragma unroll
@@ -249,13 +249,13 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
                     for (int k = 1; k < 16; ++k) dout[k] += wc1[i * 32 + 15 + k] * di;
                 }
-                march_wave_sync();
+                wave_sync();
                 // density W2: dW2[o][i] += dout[o] hd[i]
 #pragma unroll
                 for (int k = 0; k < 16; ++k) rowA[k] = dout[k];
-                march_wave_sync();
-                bwd_outer<1, 4>(slab + BWD_OFF_D2, 64, sA, sH, MARCH_HRS, sLive, lane);
-                const _Float16* hd = reinterpret_cast<const _Float16*>(sH + lane * MARCH_HRS);
+                wave_sync();
+                bwd_outer<1, 4>(slab + BWD_OFF_D2, 64, sA, sH, NGP_HRS, sLive, lane);
+                const _Float16* hd = reinterpret_cast<const _Float16*>(sH + lane * NGP_HRS);
                 float dh[64];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) {
@@ -273,51 +273,35 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
                     for (int k = 0; k < 32; ++k) de[k] += wd1[i * 32 + k] * di;
                 }
-                march_wave_sync();
+                wave_sync();
 #pragma unroll
                 for (int i = 0; i < 64; ++i) rowA[i] = dh[i];
-                // ---- hash encoding: the forward's corners again (march_density's arithmetic); the encoding goes back into sX for dW1 of the
-                // density net, the gradient into the table with one fp32 atomic add per corner and feature
+                // ---- hash encoding: the forward's corners again (ngp_level_corners of ngp_field.h, as march_density); the encoding goes back into
+                // sX for dW1 of the density net, the gradient into the table with one fp32 atomic add per corner and feature
                 if (surv) {
                     float u[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        u[k] = (x[k] - a.model[k]) / (a.model[3 + k] - a.model[k]);
-                        u[k] = fminf(fmaxf(u[k], 0.f), 1.f);
-                    }
-                    _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * MARCH_XRS);
+                    (void)ngp_unit_cube(x, a.model, a.model + 3, 0, u);
+                    _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * NGP_XRS);
 #pragma unroll 2
                     for (int l = 0; l < 16; ++l) {
-                        const float sc = a.lv.scale[l];
-                        const uint32_t res = a.lv.res[l], size = a.lv.size[l], hashed = a.lv.hashed[l];
                         const _Float16* tl = a.table + (size_t)a.lv.offset[l] * 2;
                         float* gl = a.grad_table + (size_t)a.lv.offset[l] * 2;
-                        float wt3[3];
-                        uint32_t gc[3];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) { const float pos = u[k] * sc + 0.5f; const float fl = floorf(pos); gc[k] = (uint32_t)fl; wt3[k] = pos - fl; }
                         float f0 = 0.f, f1 = 0.f;
                         const float e0 = de[2 * l], e1 = de[2 * l + 1];
-#pragma unroll
-                        for (int corner = 0; corner < 8; ++corner) {
-                            const uint32_t cx = gc[0] + (corner & 1), cy = gc[1] + ((corner >> 1) & 1), cz = gc[2] + ((corner >> 2) & 1);
-                            const float wt = ((corner & 1) ? wt3[0] : 1.f - wt3[0]) * ((corner & 2) ? wt3[1] : 1.f - wt3[1]) * ((corner & 4) ? wt3[2] : 1.f - wt3[2]);
-                            const size_t idx = (size_t)vgrid_index(cx, cy, cz, res, size, hashed) * 2;
-                            union { uint32_t u32; _Float16 h[2]; } cv;
-                            cv.u32 = *reinterpret_cast<const uint32_t*>(tl + idx);
-                            f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
-                            unsafeAtomicAdd(gl + idx, wt * e0);
-                            unsafeAtomicAdd(gl + idx + 1, wt * e1);
-                        }
+                        ngp_level_corners(a.lv, l, u, [&](size_t e, float wt) {
+                            ngp_corner_accumulate(tl, e, wt, f0, f1);
+                            unsafeAtomicAdd(gl + e, wt * e0);
+                            unsafeAtomicAdd(gl + e + 1, wt * e1);
+                        });
                         xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
                     }
                 }
-                march_wave_sync();
+                wave_sync();
                 // density W1: dW1[i][k] += dh[i] enc[k]
-                bwd_outer<4, 2>(slab + BWD_OFF_D1, 32, sA, sX, MARCH_XRS, sLive, lane);
+                bwd_outer<4, 2>(slab + BWD_OFF_D1, 32, sA, sX, NGP_XRS, sLive, lane);
             }
             if (have && T_all < a.eps) active = false;           // transmittance below early_stop_eps: the ray ends
-            march_wave_sync();
+            wave_sync();
         }
     }
 }
@@ -398,7 +382,7 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
     a.w1 = b16; a.w2 = b16 + 2048; a.table = b16 + 3072;
     a.cw1 = c16; a.cw2 = c16 + 2048; a.cw3 = c16 + 6144;
     a.wf = (const float*)ws;
-    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
+    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
     for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
     a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;
     a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;

@@ -7,11 +7,11 @@
 // One lane = one ray, 64 rays per wave march in lock step: every lane advances to its next lattice sample
 // t_mid = t_min + (n + 1/2) dt that falls in an occupied cell of the 128^3 binary grid (empty cells are skipped to the
 // cell's exit, as nerfacc does), the wave evaluates the 64 densities together (hash-grid gather per lane, 32->64->16 MLP on
-// fp16 MFMA through LDS, as ngp_density_kernel), then each lane updates T and max(alpha*T).  Only the binary label is
+// fp16 MFMA through LDS: march_density over ngp_field.h), then each lane updates T and max(alpha*T).  Only the binary label is
 // needed, so a ray stops as soon as the label is decided: hit (max >= cut_off), or T < max(cut_off, early_stop_eps)
 // (alpha*T <= T can no longer reach cut_off) — no sample list, no later samples evaluated.  Labels of a point are OR-ed
 // over cameras with one atomic per hit.  nerfacc 0.3.5 / tcnn are absent from the reference tree: parity unpinned.
-#include "march.h"      // NgpLevelsV, vgrid_index, the lattice advance and the density MLP shared with render.hip
+#include "march.h"      // the lattice advance and the density of a wave's samples, shared with render.hip (field: ngp_field.h)
 #include <cstring>
 struct VisArgs {
     const float* cams;     // [Nc,3] camera centres
@@ -19,7 +19,7 @@ struct VisArgs {
     const uint8_t* binary; // [rx,ry,rz] occupancy
     int* label;            // [Np] OR over cameras
     const _Float16 *table, *w1, *w2;
-    NgpLevelsV lv;
+    NgpLevels lv;
     float roi[6], scene[6], model[6];
     int rx, ry, rz, Nc, Np;
     float dt, cut_off, early_eps, alpha_thre;
@@ -29,50 +29,51 @@ struct VisArgs {
     unsigned long long* queue;   // persistent forms: this block's ray counter (zeroed by the caller)
 };
 
+// The ray from camera c to point p: origin o, unit direction d, t_max = their distance, t_min from the slab test against the scene aabb
+// (marching starts at max(near, 0)).  Returns whether there is anything to march.
+__device__ __forceinline__ bool vis_ray_setup(const VisArgs& a, int c, int p, float (&o)[3], float (&d)[3], float& tmin, float& tmax)
+{
+    float n2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[k] = a.cams[c * 3 + k]; d[k] = a.pts[(long)p * 3 + k] - o[k]; n2 += d[k] * d[k]; }
+    tmax = sqrtf(n2);
+    const float inv = tmax > 0.f ? 1.f / tmax : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] *= inv;
+    float near = -1e30f, far = 1e30f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float id = 1.f / d[k];
+        float t0 = (a.scene[k] - o[k]) * id, t1 = (a.scene[3 + k] - o[k]) * id;
+        if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
+        near = fmaxf(near, t0); far = fminf(far, t1);
+    }
+    tmin = fmaxf(near, 0.f);
+    return (near <= far) && far > 0.f && tmax > 0.f;
+}
+
+// The lock-step launch: the plain statement of the labels, which the persistent form below (queue, refill, coarse-cell skip, march_advance)
+// is tested against — so it keeps its OWN advance loop and transmittance update, and shares only the density of a sample (march_density).
 __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
 {
-    constexpr int XRS = 32 * 2 + 16, HRS = 64 * 2 + 16;
-    __shared__ __attribute__((aligned(16))) char smem[64 * XRS + 64 * HRS + 64 * 4];
+    __shared__ __attribute__((aligned(16))) char smem[64 * NGP_XRS + 64 * NGP_HRS + 64 * 4];
     char* sX = smem;
-    char* sH = sX + 64 * XRS;
-    float* sOut = reinterpret_cast<float*>(sH + 64 * HRS);
+    char* sH = sX + 64 * NGP_XRS;
+    float* sOut = reinterpret_cast<float*>(sH + 64 * NGP_HRS);
     const int lane = threadIdx.x;
     const long ray = (long)blockIdx.x * 64 + lane;
     const long nrays = (long)a.Nc * a.Np;
     bool done = ray >= nrays;
     const int c = done ? 0 : (int)(ray / a.Np), p = done ? 0 : (int)(ray - (long)c * a.Np);
     float o[3], d[3], tmax = 0.f, tmin = 0.f;
-    {
-        float n2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { o[k] = a.cams[c * 3 + k]; d[k] = a.pts[(long)p * 3 + k] - o[k]; n2 += d[k] * d[k]; }
-        tmax = sqrtf(n2);
-        const float inv = tmax > 0.f ? 1.f / tmax : 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) d[k] *= inv;
-        // slab test against the scene aabb; marching starts at max(near, 0)
-        float near = -1e30f, far = 1e30f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float id = 1.f / d[k];
-            float t0 = (a.scene[k] - o[k]) * id, t1 = (a.scene[3 + k] - o[k]) * id;
-            if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
-            near = fmaxf(near, t0); far = fminf(far, t1);
-        }
-        if (!(near <= far) || far <= 0.f || tmax <= 0.f) done = true;
-        tmin = fmaxf(near, 0.f);
-    }
+    if (!vis_ray_setup(a, c, p, o, d, tmin, tmax)) done = true;
     float T = 1.f, best = 0.f;
     int n = 0;
     const float roi_ext[3] = {a.roi[3] - a.roi[0], a.roi[4] - a.roi[1], a.roi[5] - a.roi[2]};
     const int rdim[3] = {a.rx, a.ry, a.rz};
     const float stop_T = fmaxf(a.cut_off, a.early_eps);
-    const int fr = lane & 15, kg = lane >> 4;
-    f16x8_t w1f[4], w2f[2];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) w1f[cb] = *reinterpret_cast<const f16x8_t*>(a.w1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) w2f[kb] = *reinterpret_cast<const f16x8_t*>(a.w2 + fr * 64 + kb * 32 + kg * 8);
+    NgpDensityW dw;
+    ngp_load_density_w(dw, a.w1, a.w2, lane);
 
     for (int iter = 0; iter < a.max_steps; ++iter) {
         // ---- advance to the next lattice sample inside an occupied cell
@@ -105,66 +106,8 @@ __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
             n += 1 + max(skip, 0);
         }
         if (!__any(have)) break;
-        // ---- density of the 64 samples (as ngp_density_kernel)
-        float u[3];
-        bool inside_m = have;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u[k] = (x[k] - a.model[k]) / (a.model[3 + k] - a.model[k]);
-            inside_m = inside_m && u[k] > 0.f && u[k] < 1.f;
-            u[k] = fminf(fmaxf(u[k], 0.f), 1.f);
-        }
-#pragma unroll 1
-        for (int l = 0; l < 16; ++l) {
-            float f0 = 0.f, f1 = 0.f;
-            if (have) {
-                const float sc = a.lv.scale[l];
-                const uint32_t res = a.lv.res[l], size = a.lv.size[l], hashed = a.lv.hashed[l];
-                const _Float16* tl = a.table + (size_t)a.lv.offset[l] * 2;
-                float w[3];
-                uint32_t g[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { const float pos = u[k] * sc + 0.5f; const float fl = floorf(pos); g[k] = (uint32_t)fl; w[k] = pos - fl; }
-#pragma unroll
-                for (int corner = 0; corner < 8; ++corner) {
-                    const uint32_t cx = g[0] + (corner & 1), cy = g[1] + ((corner >> 1) & 1), cz = g[2] + ((corner >> 2) & 1);
-                    const float wt = ((corner & 1) ? w[0] : 1.f - w[0]) * ((corner & 2) ? w[1] : 1.f - w[1]) * ((corner & 4) ? w[2] : 1.f - w[2]);
-                    union { uint32_t u32; _Float16 h[2]; } cv;
-                    cv.u32 = *reinterpret_cast<const uint32_t*>(tl + (size_t)vgrid_index(cx, cy, cz, res, size, hashed) * 2);
-                    f0 += wt * (float)cv.h[0]; f1 += wt * (float)cv.h[1];
-                }
-            }
-            _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * XRS);
-            xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
-        }
-        __syncthreads();
-        f32x4_t acc[4][4];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            const f16x8_t af = *reinterpret_cast<const f16x8_t*>(sX + (rb * 16 + fr) * XRS + kg * 16);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, w1f[cb], (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    reinterpret_cast<_Float16*>(sH + (rb * 16 + kg * 4 + r) * HRS)[cb * 16 + fr] = (_Float16)fmaxf(acc[rb][cb][r], 0.f);
-        __syncthreads();
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            f32x4_t ov = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8_t*>(sH + (rb * 16 + fr) * HRS + (kb * 32 + kg * 8) * 2), w2f[kb], ov, 0, 0, 0);
-            if (fr == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sOut[rb * 16 + kg * 4 + r] = (float)(_Float16)ov[r];
-            }
-        }
-        __syncthreads();
+        // ---- density of the 64 samples
+        const bool inside_m = march_density<false>(have, x, a.model, a.lv, a.table, dw, sX, sH, sOut, lane);
         if (have) {
             const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
             const float alpha = 1.f - __expf(-sigma * a.dt);
@@ -174,7 +117,7 @@ __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
             ++n;
             if (best >= a.cut_off || T < stop_T) done = true;
         }
-        __syncthreads();
+        wave_sync();
     }
     if (ray < nrays && best >= a.cut_off) atomicOr(a.label + p, 1);
 }
@@ -185,21 +128,17 @@ __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
 // is marched from all the others.  Here a wave keeps its 64 lanes full: a lane whose ray is decided takes the next ray from a queue
 // (one atomic per wave and refill), and a ray whose point already carries the label is not marched at all (rays are queued camera by
 // camera, so the later cameras mostly find the label set).  Per-ray arithmetic is unchanged: the labels are the same.
-// The MLP stores its hidden layer as in ngp_density_kernel: products formed transposed (weights as the MFMA's first operand), so a lane
-// holds four consecutive hidden units of one sample and writes them with one 8-byte LDS store instead of 64 two-byte ones.
 #ifdef DREG_PROBE
 __device__ long g_pass_bound = 1L << 22;   // passes of the march loop per wave (test hook of the measurement build: dreg_visibility_set_pass_bound)
 #else
 static constexpr long g_pass_bound = 1L << 22;
 #endif
-__device__ __forceinline__ void vwave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long long* __restrict__ queue)
 {
-    constexpr int XRS = MARCH_XRS, HRS = MARCH_HRS;
-    __shared__ __attribute__((aligned(16))) char smem[64 * XRS + 64 * HRS + 64 * 4];
+    __shared__ __attribute__((aligned(16))) char smem[64 * NGP_XRS + 64 * NGP_HRS + 64 * 4];
     char* sX = smem;
-    char* sH = sX + 64 * XRS;
-    float* sOut = reinterpret_cast<float*>(sH + 64 * HRS);
+    char* sH = sX + 64 * NGP_XRS;
+    float* sOut = reinterpret_cast<float*>(sH + 64 * NGP_HRS);
     const int lane = threadIdx.x;
     // the coarse occupancy (one bit per 4^3 cells) in LDS: a ray walks the empty space of a block — from the aabb's face to the surface —
     // in coarse cells looked up here (~100 cycles) instead of fine cells looked up in global memory (a dependent load of 1-2 us each);
@@ -218,8 +157,8 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
     for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
     g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
     const float stop_T = fmaxf(a.cut_off, a.early_eps);
-    MarchDensityW dw;
-    march_load_density_w(dw, a.w1, a.w2, lane);
+    NgpDensityW dw;
+    ngp_load_density_w(dw, a.w1, a.w2, lane);
 
     // per-lane ray state
     bool active = false, exhausted = false;
@@ -245,22 +184,7 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
                     const int c = (int)(ray / (unsigned long long)a.Np);
                     p = (int)(ray - (unsigned long long)c * (unsigned long long)a.Np);
                     if (__hip_atomic_load(a.label + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {      // not yet seen from an earlier camera (device-scope load: other waves set it)
-                        float n2 = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) { o[k] = a.cams[c * 3 + k]; d[k] = a.pts[(long)p * 3 + k] - o[k]; n2 += d[k] * d[k]; }
-                        tmax = sqrtf(n2);
-                        const float inv = tmax > 0.f ? 1.f / tmax : 0.f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) d[k] *= inv;
-                        float near = -1e30f, far = 1e30f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            const float id = 1.f / d[k];
-                            float t0 = (a.scene[k] - o[k]) * id, t1 = (a.scene[3 + k] - o[k]) * id;
-                            if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
-                            near = fmaxf(near, t0); far = fminf(far, t1);
-                        }
-                        if ((near <= far) && far > 0.f && tmax > 0.f) { active = true; tmin = fmaxf(near, 0.f); T = 1.f; best = 0.f; n = 0; }
+                        if (vis_ray_setup(a, c, p, o, d, tmin, tmax)) { active = true; T = 1.f; best = 0.f; n = 0; }
                     }
                 }
             }
@@ -288,7 +212,7 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
             // duration is its LONGEST ray — typically a camera on the far side marching through the whole block — not its average one)
             else if ((it & 3) == 3 && __hip_atomic_load(a.label + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) active = false;
         }
-        vwave_sync();
+        wave_sync();
     }
     // the bound was reached with rays still queued or in flight: their points stay unlabelled — say so in bit 63 of the ray counter
     // (the caller reads it back: dreg_nerf_amd/visibility.py raises on the next call)
@@ -336,6 +260,22 @@ int dreg_occupancy_coarse_bits(const uint8_t* binary, uint32_t* bits, int rx, in
     return DREG_OK;
 }
 
+static void vis_fill(VisArgs& a, const float* cams, const float* pts, const uint8_t* binary, int* label, const void* table, const void* w1, const void* w2,
+                     const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                     const float* roi_aabb, const float* scene_aabb, const float* model_aabb, int rx, int ry, int rz, int Nc, int Np,
+                     float render_step_size, float cut_off, float early_stop_eps, float alpha_thre, void* queue, const uint32_t* coarse_bits)
+{
+    a.cams = cams; a.pts = pts; a.binary = binary; a.label = label;
+    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
+    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
+    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
+    a.rx = rx; a.ry = ry; a.rz = rz; a.Nc = Nc; a.Np = Np;
+    a.dt = render_step_size; a.cut_off = cut_off; a.early_eps = early_stop_eps; a.alpha_thre = alpha_thre;
+    a.max_steps = 1 << 16;
+    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
+    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;      // (the kernel keeps the bits in 4 KB of LDS)
+    a.queue = (unsigned long long*)queue;
+}
 // label[p] = OR over cameras of (max_samples alpha*T >= cut_off) along the ray camera -> point p (must be zeroed by the caller).
 // table/w1/w2: fp16 inference copies of mlp_base.params; level arrays / aabbs are HOST pointers (16 entries / 6 floats).
 int dreg_surface_visibility(const float* cams, const float* pts, const uint8_t* binary, int* label,
@@ -347,34 +287,12 @@ int dreg_surface_visibility(const float* cams, const float* pts, const uint8_t* 
 {
     if ((long)Nc * Np == 0) return DREG_OK;
     VisArgs a;
-    a.cams = cams; a.pts = pts; a.binary = binary; a.label = label;
-    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
-    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
-    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
-    a.rx = rx; a.ry = ry; a.rz = rz; a.Nc = Nc; a.Np = Np;
-    a.dt = render_step_size; a.cut_off = cut_off; a.early_eps = early_stop_eps; a.alpha_thre = alpha_thre;
-    a.max_steps = 1 << 16;
-    a.coarse = nullptr; a.cx = a.cy = a.cz = 0; a.queue = nullptr;
+    vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
+             render_step_size, cut_off, early_stop_eps, alpha_thre, nullptr, nullptr);
     const long nrays = (long)Nc * Np;
     hipLaunchKernelGGL(surface_visibility_kernel, dim3((unsigned)((nrays + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
-}
-static void vis_fill(VisArgs& a, const float* cams, const float* pts, const uint8_t* binary, int* label, const void* table, const void* w1, const void* w2,
-                     const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
-                     const float* roi_aabb, const float* scene_aabb, const float* model_aabb, int rx, int ry, int rz, int Nc, int Np,
-                     float render_step_size, float cut_off, float early_stop_eps, float alpha_thre, void* queue, const uint32_t* coarse_bits)
-{
-    a.cams = cams; a.pts = pts; a.binary = binary; a.label = label;
-    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
-    for (int l = 0; l < 16; ++l) { a.lv.offset[l] = offset[l]; a.lv.size[l] = size[l]; a.lv.res[l] = res[l]; a.lv.scale[l] = scale[l]; a.lv.hashed[l] = hashed[l]; }
-    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
-    a.rx = rx; a.ry = ry; a.rz = rz; a.Nc = Nc; a.Np = Np;
-    a.dt = render_step_size; a.cut_off = cut_off; a.early_eps = early_stop_eps; a.alpha_thre = alpha_thre;
-    a.max_steps = 1 << 16;
-    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
-    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;      // (the kernel keeps the bits in 4 KB of LDS)
-    a.queue = (unsigned long long*)queue;
 }
 // Descriptor-table form for several blocks per launch.  The caller owns the table: n records of dreg_surface_visibility_desc_bytes() bytes,
 // filled ON THE HOST by dreg_surface_visibility_fill_desc (same arguments as dreg_surface_visibility_queue, one block each), copied to
