@@ -47,6 +47,10 @@ def config_parser(argv=None):
                    help="eval: per scene, transformation_est.json and the registration's point clouds as PLY files (eval_nerf_regtr.py:313-438)")
     p.add_argument("--render_views", action="store_true",
                    help="eval: per scene, render both NeRF blocks under the ground-truth, predicted and no alignment (render_videos, eval_nerf_regtr.py:113-172,345-369)")
+    p.add_argument("--eval_images", action="store_true",
+                   help="eval_ngp_nerf.py: render the held-out views of --scene and write PSNR / SSIM per view to eval/<scene>/[block_k/]metrics.json (evaluate, eval_ngp_nerf.py:159-244 of the reference)")
+    p.add_argument("--point_cloud", action="store_true",
+                   help="eval_ngp_nerf.py: depth-range point cloud of the block's training cameras, point_cloud.ply next to the checkpoint (generate_point_cloud, eval_ngp_nerf.py:246-334 of the reference)")
     p.add_argument("--fgr_baseline", action="store_true",
                    help="also run the Fast Global Registration baseline on every pair and write fgr_metrics_{split}.json (eval_nerf_regtr.py:303-311 of the reference)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")

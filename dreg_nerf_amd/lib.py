@@ -246,6 +246,9 @@ SIGNATURES = {
     "dreg_ngp_render_bwd_workspace_bytes": (Z, [ctypes.c_long]),
     "dreg_ngp_render_bwd": (I, [P, P, P, ctypes.c_long, P, I, I, I, P, P, P] + [P] * 5 + [P, P, P] + [F] * 5 + [P, P, P, P, P, Z, P]),
     "dreg_ngp_adam_step": (I, [P] * 5 + [Z, F, F, F, F, I, P]),
+    # image_metrics.hip
+    "dreg_image_metrics_workspace_bytes": (Z, [I, I, I, I]),
+    "dreg_image_metrics": (I, [P, P, I, I, I, I, P] + [P] * 6 + [P, Z, P]),
 }
 
 

@@ -757,6 +757,18 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
                         const float* rgb, const float* grad_rgb, float* grad_base, float* grad_color, void* workspace, size_t workspace_bytes, void* stream);
 int dreg_ngp_adam_step(float* p, float* g, float* m, float* v, void* p16, size_t n, float lr, float beta1, float beta2, float eps, int step, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- image metrics of rendered views
+ * (csrc/image_metrics.hip; rule: DESIGN.md §3d) SSIM, MSE and PSNR of the reference's evaluate() (eval_ngp_nerf.py:24-31,214-229,
+ * conerf/loss/ssim_torch.py) for N image pairs in one call.  pred, gt: fp32 [N,H,W,C], channel-last, contiguous, device; 1 <= C <= 4,
+ * H, W >= 1, N <= 65535.  taps: the 11 fp32 window taps in HOST memory (read during the call).  ssim, mse, psnr: fp32 [N] on the device,
+ * written on `stream` without a host synchronisation; psnr = -10 ln(mse + 1e-6) / ln 10.  Optional (null = not written): ssim_map fp32
+ * [N,H,W,C]; pred_u8 / gt_u8 uint8 [N,H,W,C] = trunc(clamp(v, 0, 1) * 255).  workspace: dreg_image_metrics_workspace_bytes(N,H,W,C) bytes of
+ * device memory, 8-byte aligned (per-tile fp64 sums; 0 = unsupported shape).  No atomics: bit-identical between runs; pred == gt gives
+ * ssim = 1, mse = 0, psnr = 60 exactly. */
+size_t dreg_image_metrics_workspace_bytes(int N, int H, int W, int C);
+int dreg_image_metrics(const float* pred, const float* gt, int N, int H, int W, int C, const float* taps, float* ssim, float* mse, float* psnr,
+                       float* ssim_map, uint8_t* pred_u8, uint8_t* gt_u8, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
