@@ -16,11 +16,33 @@ struct MarchGrid {
     int rdim[3], ry, rz, cy, cz;
 };
 
+// Rounding allowance, in position, of a lattice sample's distance to a cell face on one axis.  A sample's fp32 coordinate
+// x = fl(o + fl(t d)) with t = fl(t_min + fl((n + 1/2) dt)) is within 2^-24 (|o| + 6 |t d|) of the exact line, and its cell index
+// floor(fl(fl(fl(x - lo) / ext) res)) moves it by at most 4 * 2^-24 ext more; |t d| <= |o| + m inside the roi, where m is the larger of
+// |lo| and |hi|, and ext <= 2 m.  That bounds the current sample, the face and any later sample of the same cell together by
+// 2^-24 (7 |o| + 14 m) each; the allowance is 2^-19 (|o| + m), above twice that.
+__device__ __forceinline__ float march_face_slack(float o_k, float roi_lo_k, float roi_hi_k)
+{
+    return 0x1p-19f * (fabsf(o_k) + fmaxf(fabsf(roi_lo_k), fabsf(roi_hi_k)));
+}
+// Lattice points a ray may pass over between a sample at distance `gap` (>= 0, along one axis with direction component d_k != 0) from the
+// face through which it leaves its empty cell, and that face: those whose fp32 position is still inside the cell WHATEVER the rounding, i.e.
+// at most (gap - slack) / (|d_k| dt) steps ahead, less 2^-20 relative for the roundings of the two quotients.  (The constant allowance this
+// replaces, 1e-3 of a step, is less than the rounding of x once |d_k| dt is below ~1e-4: nearly axis-parallel rays at dt = 1e-3 lost a sample.)
+__device__ __forceinline__ float march_steps_to_face(float gap, float slack, float d_k, float dt)
+{
+    return fmaxf(gap - slack, 0.f) / (fabsf(d_k) * dt) * (1.f - 0x1p-20f);
+}
+
 // Advance one live ray (active) to its next lattice sample inside an occupied cell, at most `guard_max` cells per call.  On return:
 // true = a sample at t_mid = *tm_out, position x;  false with active cleared = the ray has left [t_min, t_max);
 // false with active set = the guard ran out inside empty space (the caller continues on its next pass).  A point outside the roi is
-// unoccupied; an inside point's cell is floor(u * res) clamped to the grid.  The skip over an empty (coarse) cell passes over only the
-// lattice points strictly inside it (a conservative floor): the same lattice samples are visited as by stepping one by one.
+// unoccupied; an inside point's cell is floor(u * res) clamped to the grid.
+// CONTRACT of the skip: from a sample in an empty cell (or, with the coarse bits, an empty 4^3 block) the ray passes over only lattice points
+// whose fp32 position, evaluated exactly as this loop evaluates it, lies in that same cell: march_steps_to_face keeps the rounding allowance
+// of march_face_slack away from the exit face on every axis.  Every point passed over would therefore have been found empty, so the samples
+// returned are the ones stepping through every lattice point returns — with or without coarse bits, for any direction and step
+// (tests/test_hip_march_exact.py).  Within the allowance of the face the ray steps one lattice point at a time.
 __device__ __forceinline__ bool march_advance(const MarchGrid& g, const float (&o)[3], const float (&d)[3], float tmin, float tmax, float dt, int& n, bool& active, float (&x)[3], float* tm_out, int guard_max)
 {
     for (int guard = 0; active && guard < guard_max; ++guard) {
@@ -46,19 +68,18 @@ __device__ __forceinline__ bool march_advance(const MarchGrid& g, const float (&
             else occ = g.binary[((long)ci[0] * g.ry + ci[1]) * g.rz + ci[2]] != 0;
         }
         if (occ) { if (tm_out) *tm_out = tm; return true; }
-        float texit = 1e30f;
+        float steps = 1e9f;                                                            // lattice steps to the exit face, rounding allowed for
         if (inside) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 if (d[k] != 0.f) {
                     const int hi = min(cell_lo[k] + cell_w, g.rdim[k]);                // (a ragged last coarse cell ends at the grid's face)
                     const float face = g.roi[k] + (float)(d[k] > 0.f ? hi : cell_lo[k]) * g.roi_ext[k] / (float)g.rdim[k];
-                    texit = fminf(texit, fmaxf((face - x[k]) / d[k], 0.f));
+                    steps = fminf(steps, march_steps_to_face(fabsf(face - x[k]), march_face_slack(o[k], g.roi[k], g.roi[3 + k]), d[k], dt));
                 }
             }
-        } else texit = 0.f;
-        const int skip = (int)floorf(texit / dt - 1e-3f);
-        n += 1 + max(skip, 0);
+        } else steps = 0.f;
+        n += 1 + max((int)floorf(steps), 0);
     }
     return false;
 }

@@ -91,19 +91,19 @@ __global__ __launch_bounds__(64) void surface_visibility_kernel(VisArgs a)
             for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)rdim[k]), 0), rdim[k] - 1);
             const bool occ = inside && a.binary[((long)ci[0] * a.ry + ci[1]) * a.rz + ci[2]] != 0;
             if (occ) { have = true; break; }
-            // skip to the exit of this cell (or, outside the roi, just step): smallest positive distance to a cell face
-            float texit = 1e30f;
+            // skip to the exit of this cell (or, outside the roi, just step): only lattice points that stay in the cell whatever the rounding
+            // (march.h: the contract of the skip and its allowance, march_face_slack / march_steps_to_face)
+            float steps = 1e9f;
             if (inside) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     if (d[k] != 0.f) {
                         const float face = a.roi[k] + (float)(ci[k] + (d[k] > 0.f ? 1 : 0)) * roi_ext[k] / (float)rdim[k];
-                        texit = fminf(texit, fmaxf((face - x[k]) / d[k], 0.f));
+                        steps = fminf(steps, march_steps_to_face(fabsf(face - x[k]), march_face_slack(o[k], a.roi[k], a.roi[3 + k]), d[k], a.dt));
                     }
                 }
-            } else texit = 0.f;
-            const int skip = (int)floorf(texit / a.dt - 1e-3f);   // lattice points strictly inside the remaining empty stretch (conservative)
-            n += 1 + max(skip, 0);
+            } else steps = 0.f;
+            n += 1 + max((int)floorf(steps), 0);
         }
         if (!__any(have)) break;
         // ---- density of the 64 samples
