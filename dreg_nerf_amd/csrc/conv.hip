@@ -2047,6 +2047,8 @@ __global__ void pack_weight_dgrad_kernel(const float* __restrict__ w, T* __restr
 // ------------------------------------------------------------------------------------------------
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// K extent of a packed weight row: ksz^3 taps x Cin channels, padded to whole 128-byte K steps
+static int conv_kpad(int ksz, int Cin, int esize) { const int bke = 128 / esize; return ((ksz * ksz * ksz * Cin + bke - 1) / bke) * bke; }
 
 static int fill_geom(ConvGeom& g, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
                      int ksz, int stride, int pad, int transposed, int esize)
@@ -2064,8 +2066,7 @@ static int fill_geom(ConvGeom& g, int B, int Di, int Hi, int Wi, int Cin, int Do
     if ((uint64_t)B * Di * Hi * Wi * Cin * esize >= (1ull << 40)) return DREG_EINVAL;
     g.M = (uint32_t)M;
     g.magW = host_magic(Wo); g.magH = host_magic(Ho); g.magD = host_magic(Do);
-    const int bke = 128 / esize;
-    g.Kpad = ((g.ntaps * Cin + bke - 1) / bke) * bke;
+    g.Kpad = conv_kpad(ksz, Cin, esize);
     return DREG_OK;
 }
 
@@ -2110,165 +2111,145 @@ DREG_KNOB(int, g_igemm_ap256, 1);         // tuning (include/dreg_nerf_probe.h):
 struct SplitkDefer { int* nsplit; size_t* slice; };   // out arguments of dreg_conv3d_igemm_defer (null = always reduce)
 DREG_KNOB(int, g_igemm_ap, 256);          // tuning (include/dreg_nerf_probe.h): launches of at most this many 128-row tiles take the eight-wave anti-phase form (0: never)
 DREG_KNOB(int, g_narrow_small, 2);        // tuning (include/dreg_nerf_probe.h): 128 x 64 tiles for launches of < 224 128 x 128 tiles
-// Which kernel instantiation a bf16 / fp32 convolution launch runs (ONE rule set: launch_conv dispatches on it and
-// dreg_conv3d_igemm_variant reports it, so profiler labels name the launched template arguments — the row rocprofv3 prints).
-struct IgemmChoice { int kind, bm, bn, ap, ksplit; };   // kind 0: direct-to-LDS kernel, 1: register-staged kernel, -1: unsupported
-static IgemmChoice igemm_choose(const ConvGeom& g, uint32_t nrows, bool rowlist, bool has_ws, bool has_addend, int esize)
+DREG_KNOB(int, g_bn_stats_epilogue, 1);   // probe knob (include/dreg_nerf_probe.h): dreg_conv3d_igemm_bnstats leaves the class sums behind
+// Which kernel instantiation a bf16 / fp32 convolution launch runs, and with which launch arguments.  ONE rule set: launch_conv launches
+// from it, dreg_conv3d_igemm_workspace_bytes / _bnstats / _defer read their split-K and tile facts from it, and dreg_conv3d_igemm_variant
+// encodes it, so profiler labels name the launched template arguments — the row rocprofv3 prints.
+struct IgemmChoice {
+    int kind;                  // 0: direct-to-LDS kernel (conv_igemm_glds_kernel), 1: register-staged kernel (conv_igemm_kernel), -1: unsupported
+    int bm, bn, ap, dbg;       // tile and the AP / DBG template arguments (dbg: the instrumented kernel of dreg_conv_igemm_probe)
+    int ksplit;                // K slices over blockIdx.y (1 = no split-K; > 1: fp32 partial tiles + splitk_reduce_kernel)
+    int stages, threads;       // LDS stages (kernel argument) and workgroup size
+    int tiles_m, tiles_n;      // grid = tiles_m * tiles_n x ksplit
+    size_t lds;                // dynamic LDS bytes
+    bool fits;                 // both operands are within the 2 GiB reach of the direct-to-LDS kernel's buffer descriptors
+};
+// out_esize: element size of the output (the probe kernel exists for bf16 output only)
+static IgemmChoice igemm_choose(const ConvGeom& g, uint32_t nrows, bool rowlist, bool has_ws, bool has_addend, int esize, int out_esize)
 {
-    IgemmChoice c{1, 128, g.Cout % 128 == 0 ? 128 : 64, 0, 1};
+    IgemmChoice c{1, 128, g.Cout % 128 == 0 ? 128 : 64, 0, 0, 1, 2, 256, 0, 0, 0, false};
+    const uint32_t tm_ = (nrows + 127) / 128;
     if (esize == 2) {
         const uint64_t in_bytes = (uint64_t)g.B * g.Di * g.Hi * g.Wi * g.Cin * 2, wt_bytes = (uint64_t)g.Cout * g.Kpad * 2;
-        const bool fits = in_bytes < 0x7fffff00ull && wt_bytes < 0x7fffff00ull;
+        c.fits = in_bytes < 0x7fffff00ull && wt_bytes < 0x7fffff00ull;
         const int ksplit = (has_ws && !rowlist) ? conv_ksplit(g, has_addend) : 1;
-        if (ksplit > 1 && fits) {
-            const int tm_ = (g.M + 127) / 128;
-            c.kind = 0; c.ksplit = ksplit; c.bn = g.Cout % 128 == 0 ? 128 : 64;
-            c.ap = (g_igemm_ap && tm_ * (g.Cout / c.bn) * ksplit <= g_igemm_ap) ? 1 : 0;
-            return c;
-        }
-        if (g_use_glds && g.sd == 1 && g.Cin % 64 == 0 && g.ntaps <= 32 && fits) {
+        if (ksplit > 1 && c.fits) {
+            c.kind = 0; c.ksplit = ksplit;
+            c.ap = (g_igemm_ap && (int)tm_ * (g.Cout / c.bn) * ksplit <= g_igemm_ap) ? 1 : 0;
+        } else if (g_use_glds && g.sd == 1 && g.Cin % 64 == 0 && g.ntaps <= 32 && c.fits) {
             c.kind = 0;
-            const uint32_t tm_ = (nrows + 127) / 128;
             // (1^3 layers with few input channels and an addend — the accumulating data gradients of layer 1 / 2's first convolutions — are
             //  HBM-bound read-modify-write passes: the 128-row tile, two workgroups per CU and the addend fetched four rows ahead)
             const bool rmw_pointwise = g.ntaps == 1 && has_addend && g.Cin <= g_pointwise_rmw_cin;
             if (g.Cout % 256 == 0 && (g_use_glds == 1 || g_use_glds == 4 || g_use_glds == 5) && nrows >= 65536 && !rmw_pointwise) { c.bm = 256; c.bn = 256; c.ap = g_igemm_ap256 ? 1 : 0; }
             else if (g.Cout % 256 == 0 && g_use_glds == 3 && nrows >= 65536) { c.bm = 128; c.bn = 256; }
+            else if (g_igemm_probe && g.Cout % 128 == 0 && out_esize == 2) { c.bn = 128; c.dbg = 1; }
+            // launches that put at most one or two workgroups on a CU: the eight-wave anti-phase form of the same tile (bit-identical)
             else if (g_igemm_ap && g.Cout % 128 == 0 && tm_ * (g.Cout / 128) <= (uint32_t)g_igemm_ap) { c.bn = 128; c.ap = 1; }
             else if (g_igemm_ap && g.Cout % 128 != 0 && g.Cout % 64 == 0 && tm_ * (g.Cout / 64) <= (uint32_t)g_igemm_ap) { c.bn = 64; c.ap = 1; }
+            // fewer 128 x 128 tiles than CUs (the point-set half's linear layers: ~77 row tiles x 2): half-width tiles put twice as
+            // many workgroups on the chip
             else if (g.Cout % 128 == 0 && !(g_narrow_small && tm_ * (g.Cout / 128) < (uint32_t)g_narrow_thr)) c.bn = 128;
             else if (g.Cout % 64 == 0) c.bn = 64;
             else c.kind = -1;
-            return c;
         }
     }
-    if (g.Cout % 128 != 0 && g.Cout % 64 != 0) c.kind = -1;      // (row lists outside the direct-to-LDS shapes: the register-staged kernel takes them too)
+    // (row lists outside the direct-to-LDS shapes — the stem: 5^3 taps, stride 2, 8 input channels — run the register-staged kernel on the list)
+    if (c.kind == 1 && g.Cout % 128 != 0 && g.Cout % 64 != 0) c.kind = -1;
+    if (c.kind < 0) return c;
+    c.tiles_m = (nrows + c.bm - 1) / c.bm; c.tiles_n = g.Cout / c.bn;
+    if (c.kind == 0) {
+        const bool wide = c.bm == 256 && c.ap;             // the anti-phase 256 x 256 tile: 32-channel (64-byte) stages
+        c.stages = c.ap ? 4 : ((c.bn == 256 || c.dbg) ? 2 : glds_stages((long)c.tiles_m * c.tiles_n * c.ksplit));
+        c.threads = (c.bn == 256 || c.ap) ? 512 : 256;
+        c.lds = (size_t)c.stages * (c.bm + c.bn) * (wide ? 64 : 128);
+    } else c.lds = (size_t)2 * (128 + c.bn) * 128;
     return c;
+}
+// the launches whose output can carry the BatchNorm class sums of dreg_conv3d_igemm_bnstats (V = voxels per grid)
+static bool igemm_emits_bn_sums(const IgemmChoice& c, int V)
+{
+    return g_bn_stats_epilogue && c.kind == 0 && c.ksplit == 1 && V % c.bm == 0 && V % 128 == 0 &&
+           ((c.bm == 128 && c.bn <= 128) || (c.bm == 256 && c.bn == 256));   // (LDS behind the 128 x 256 tile is too small for the class sums)
+}
+
+struct ConvArgs {              // what a convolution launch passes to its kernel besides the geometry and the choice
+    const void *in, *wt; void* out; const float* bias; const void* addend;
+    int relu, Da, Ha, Wa, add_shift;
+    const int* rowlist; uint32_t nrows; float* bn_part;
+};
+template <typename TO, int BM, int BN, int DBG, int AP>
+static void igemm_glds_launch(const IgemmChoice& c, const ConvGeom& g, const ConvArgs& a, hipStream_t st)
+{
+    const uint32_t in_bytes = (uint32_t)((uint64_t)g.B * g.Di * g.Hi * g.Wi * g.Cin * 2), wt_bytes = (uint32_t)((uint64_t)g.Cout * g.Kpad * 2);
+    if (c.lds > 65536) (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<TO, BM, BN, DBG, AP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);
+    hipLaunchKernelGGL((conv_igemm_glds_kernel<TO, BM, BN, DBG, AP>), dim3(c.tiles_m * c.tiles_n, c.ksplit), dim3(c.threads), c.lds, st,
+                       (const bf16_t*)a.in, (const bf16_t*)a.wt, (TO*)a.out, a.bias, (const TO*)a.addend, g, a.relu, a.Da, a.Ha, a.Wa, a.add_shift, c.tiles_n,
+                       in_bytes, wt_bytes, a.rowlist, a.nrows, c.ksplit, c.stages, a.bn_part);
+}
+// the direct-to-LDS instantiations that exist, by the choice's template arguments
+template <typename TO>
+static int igemm_glds_dispatch(const IgemmChoice& c, const ConvGeom& g, const ConvArgs& a, hipStream_t st)
+{
+    if (c.bm == 256 && c.bn == 256 && c.ap) igemm_glds_launch<TO, 256, 256, 0, 1>(c, g, a, st);
+    else if (c.bm == 256 && c.bn == 256) igemm_glds_launch<TO, 256, 256, 0, 0>(c, g, a, st);
+    else if (c.bm == 128 && c.bn == 256) igemm_glds_launch<TO, 128, 256, 0, 0>(c, g, a, st);
+    else if (c.dbg) igemm_glds_launch<TO, 128, 128, 1, 0>(c, g, a, st);
+    else if (c.bn == 128 && c.ap) igemm_glds_launch<TO, 128, 128, 0, 1>(c, g, a, st);
+    else if (c.bn == 64 && c.ap) igemm_glds_launch<TO, 128, 64, 0, 1>(c, g, a, st);
+    else if (c.bn == 128) igemm_glds_launch<TO, 128, 128, 0, 0>(c, g, a, st);
+    else if (c.bn == 64) igemm_glds_launch<TO, 128, 64, 0, 0>(c, g, a, st);
+    else return DREG_EINVAL;
+    return DREG_OK;
 }
 
 template <typename T, typename TO>
 static int launch_conv(const void* in, const void* wt, void* out, const float* bias, const void* addend,
                        const ConvGeom& g, int relu, int Da, int Ha, int Wa, int add_shift, hipStream_t st,
                        const int* rowlist = nullptr, uint32_t nrows_in = 0, float* ks_ws = nullptr, size_t ks_ws_bytes = 0,
-                       const uint8_t* rowocc = nullptr, float* bn_part = nullptr, const SplitkDefer* defer = nullptr)
+                       const uint8_t* rowocc = nullptr, float* bn_part = nullptr, int* bn_rows_per_chunk = nullptr, const SplitkDefer* defer = nullptr)
 {
     // output-row occupancy is honoured by the register-staged kernel for plain forward gathers whose tiles are whole W-rows
     if (rowocc && (rowlist || bias || addend || relu || g.dsign != 1 || g.sd != 1 || g.Wo <= 0 || 128 % g.Wo != 0 || g.M % (uint32_t)g.Wo != 0)) rowocc = nullptr;
     const uint32_t nrows = rowlist ? nrows_in : g.M;
-    const int tilesM = (nrows + 127) / 128;
     if (rowlist && nrows == 0) return DREG_OK;
+    const IgemmChoice c = igemm_choose(g, nrows, rowlist != nullptr, ks_ws != nullptr, addend != nullptr, (int)sizeof(T), (int)sizeof(TO));
+    if (c.kind < 0) return DREG_EINVAL;
     if constexpr (sizeof(T) == 2) {
-        const uint64_t in_bytes = (uint64_t)g.B * g.Di * g.Hi * g.Wi * g.Cin * 2, wt_bytes = (uint64_t)g.Cout * g.Kpad * 2;
-        const int ksplit = (ks_ws && !rowlist) ? conv_ksplit(g, addend != nullptr) : 1;
-        if (ksplit > 1 && in_bytes < 0x7fffff00ull && wt_bytes < 0x7fffff00ull) {
+        if (c.ksplit > 1) {                                        // fp32 partial tiles per K slice, then the finishing pass
             const size_t slice = (size_t)g.M * g.Cout;
-            if (ks_ws_bytes < slice * ksplit * sizeof(float)) return DREG_EINVAL;
-            const int tm_ = (g.M + 127) / 128;
-            if (g.Cout % 128 == 0 && g_igemm_ap && tm_ * (g.Cout / 128) * ksplit <= g_igemm_ap) {
-                (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<float, 128, 128, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * 128);
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<float, 128, 128, 0, 1>), dim3(tm_ * (g.Cout / 128), ksplit), dim3(512), (size_t)4 * 256 * 128, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, ks_ws, nullptr, nullptr, g, 0, 0, 0, 0, 0, g.Cout / 128,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, nullptr, g.M, ksplit, 4, nullptr);
-            } else if (g.Cout % 128 != 0 && g_igemm_ap && tm_ * (g.Cout / 64) * ksplit <= g_igemm_ap) {
-                (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<float, 128, 64, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 192 * 128);
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<float, 128, 64, 0, 1>), dim3(tm_ * (g.Cout / 64), ksplit), dim3(512), (size_t)4 * 192 * 128, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, ks_ws, nullptr, nullptr, g, 0, 0, 0, 0, 0, g.Cout / 64,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, nullptr, g.M, ksplit, 4, nullptr);
-            } else
-            if (g.Cout % 128 == 0) {
-                const int ns = glds_stages(tm_ * (g.Cout / 128) * ksplit);
-                if (ns > 2) (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<float, 128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, ns * 256 * 128);
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<float, 128, 128>), dim3(tm_ * (g.Cout / 128), ksplit), dim3(256), (size_t)ns * 256 * 128, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, ks_ws, nullptr, nullptr, g, 0, 0, 0, 0, 0, g.Cout / 128,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, nullptr, g.M, ksplit, ns, nullptr);
-            } else {
-                const int ns = glds_stages(tm_ * (g.Cout / 64) * ksplit);
-                if (ns > 2) (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<float, 128, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, ns * 192 * 128);
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<float, 128, 64>), dim3(tm_ * (g.Cout / 64), ksplit), dim3(256), (size_t)ns * 192 * 128, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, ks_ws, nullptr, nullptr, g, 0, 0, 0, 0, 0, g.Cout / 64,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, nullptr, g.M, ksplit, ns, nullptr);
-            }
+            if (ks_ws_bytes < slice * c.ksplit * sizeof(float)) return DREG_EINVAL;
+            const ConvArgs a{in, wt, ks_ws, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, g.M, nullptr};
+            if (int rc = igemm_glds_dispatch<float>(c, g, a, st)) return rc;
             DREG_LAUNCH_CHECK();
             if (defer && !bias && !relu && sizeof(TO) == 2) {      // the consumer sums the slices (dreg_conv3d_igemm_defer's out arguments tell it)
-                *defer->nsplit = ksplit; *defer->slice = slice;
+                *defer->nsplit = c.ksplit; *defer->slice = slice;
                 return DREG_OK;
             }
             const size_t total8 = slice / 8;
             const int nb = (int)((total8 + 255) / 256 > 2048 ? 2048 : (total8 + 255) / 256);
-            hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3(nb), dim3(256), 0, st, ks_ws, (TO*)out, bias, total8, slice, g.Cout, ksplit, relu);
+            hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3(nb), dim3(256), 0, st, ks_ws, (TO*)out, bias, total8, slice, g.Cout, c.ksplit, relu);
             DREG_LAUNCH_CHECK();
             return DREG_OK;
         }
-        if (g_use_glds && g.sd == 1 && g.Cin % 64 == 0 && g.ntaps <= 32 && in_bytes < 0x7fffff00ull && wt_bytes < 0x7fffff00ull) {
-#define GL_LAUNCH(BMv, BNv, NT) do { \
-                const int tm_ = (nrows + BMv - 1) / BMv, tn_ = g.Cout / BNv; \
-                const int ns_ = BNv == 256 ? 2 : glds_stages(tm_ * tn_); \
-                const size_t lds_ = (size_t)ns_ * (BMv + BNv) * 128; \
-                if (lds_ > 65536) (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<TO, BMv, BNv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<TO, BMv, BNv>), dim3(tm_ * tn_), dim3(NT), lds_, st, \
-                                   (const bf16_t*)in, (const bf16_t*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tn_, \
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, rowlist, nrows, 1, ns_, bn_part); } while (0)
-            const IgemmChoice ch = igemm_choose(g, nrows, rowlist != nullptr, false, addend != nullptr, 2);
-            if (ch.bm == 256 && ch.ap) {
-                const int tm_ = (nrows + 255) / 256, tn_ = g.Cout / 256;
-                const size_t lds_ = (size_t)4 * (256 + 256) * 64;
-                (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<TO, 256, 256, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_);
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<TO, 256, 256, 0, 1>), dim3(tm_ * tn_), dim3(512), lds_, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tn_,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, rowlist, nrows, 1, 4, bn_part);
-            }
-            else if (ch.bm == 256) GL_LAUNCH(256, 256, 512);
-            else if (ch.bn == 256) GL_LAUNCH(128, 256, 512);
-            // fewer 128 x 128 tiles than CUs (the point-set half's linear layers: ~77 row tiles x 2): half-width tiles put twice as
-            // many workgroups on the chip
-            else if (g_igemm_probe && g.Cout % 128 == 0 && sizeof(TO) == 2) {
-                const int tm_ = (nrows + 127) / 128, tn_ = g.Cout / 128;
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<TO, 128, 128, 1>), dim3(tm_ * tn_), dim3(256), (size_t)2 * 256 * 128, st,
-                                   (const bf16_t*)in, (const bf16_t*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tn_,
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, rowlist, nrows, 1, 2, bn_part);
-            }
-#define GL_LAUNCH_AP(BNv) do { \
-                const int tm_ = (nrows + 127) / 128, tn_ = g.Cout / BNv; \
-                const size_t lds_ = (size_t)4 * (128 + BNv) * 128; \
-                (void)hipFuncSetAttribute((const void*)conv_igemm_glds_kernel<TO, 128, BNv, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<TO, 128, BNv, 0, 1>), dim3(tm_ * tn_), dim3(512), lds_, st, \
-                                   (const bf16_t*)in, (const bf16_t*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tn_, \
-                                   (uint32_t)in_bytes, (uint32_t)wt_bytes, rowlist, nrows, 1, 4, bn_part); } while (0)
-            // launches that put at most one or two workgroups on a CU: the eight-wave anti-phase form of the same tile (bit-identical)
-            else if (ch.kind == 0 && ch.ap && ch.bn == 128) GL_LAUNCH_AP(128);
-            else if (ch.kind == 0 && ch.ap && ch.bn == 64) GL_LAUNCH_AP(64);
-            else if (ch.kind == 0 && ch.bn == 128) GL_LAUNCH(128, 128, 256);
-            else if (ch.kind == 0 && ch.bn == 64) GL_LAUNCH(128, 64, 256);
-            else return DREG_EINVAL;
-#undef GL_LAUNCH
-#undef GL_LAUNCH_AP
+        if (c.kind == 0) {
+            const bool emit = bn_part && bn_rows_per_chunk && igemm_emits_bn_sums(c, g.Do * g.Ho * g.Wo);
+            const ConvArgs a{in, wt, out, bias, addend, relu, Da, Ha, Wa, add_shift, rowlist, nrows, emit ? bn_part : nullptr};
+            if (int rc = igemm_glds_dispatch<TO>(c, g, a, st)) return rc;
             DREG_LAUNCH_CHECK();
+            if (emit) *bn_rows_per_chunk = 128;                    // every tile shape writes 128-row chunk sums in one canonical order
             return DREG_OK;
         }
     }
-    // (row lists: the direct-to-LDS kernels above; shapes they do not take — the stem: 5^3 taps, stride 2, 8 input channels — run the
-    //  register-staged kernel on the list)
-    if (g.Cout % 128 == 0) {
-        const int tilesN = g.Cout / 128;
-        const size_t lds = 2 * (128 + 128) * 128;
-        hipLaunchKernelGGL((conv_igemm_kernel<T, TO, 128>), dim3(tilesM * tilesN), dim3(256), lds, st,
-                           (const T*)in, (const T*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tilesN, rowocc, rowlist, nrows);
-    } else if (g.Cout % 64 == 0) {
-        const int tilesN = g.Cout / 64;
-        const size_t lds = 2 * (128 + 64) * 128;
-        hipLaunchKernelGGL((conv_igemm_kernel<T, TO, 64>), dim3(tilesM * tilesN), dim3(256), lds, st,
-                           (const T*)in, (const T*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, tilesN, rowocc, rowlist, nrows);
-    } else return DREG_EINVAL;
+    if (c.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, TO, 128>), dim3(c.tiles_m * c.tiles_n), dim3(c.threads), c.lds, st,
+                                        (const T*)in, (const T*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, c.tiles_n, rowocc, rowlist, nrows);
+    else hipLaunchKernelGGL((conv_igemm_kernel<T, TO, 64>), dim3(c.tiles_m * c.tiles_n), dim3(c.threads), c.lds, st,
+                            (const T*)in, (const T*)wt, (TO*)out, bias, (const TO*)addend, g, relu, Da, Ha, Wa, add_shift, c.tiles_n, rowocc, rowlist, nrows);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
 }
 
 extern "C" {
-
-int dreg_conv3d_igemm_occ(const void* in, const void* wt_packed, void* out, const float* bias, const void* addend,
-                          int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                          int ksz, int stride, int pad, int transposed, int relu, int Da, int Ha, int Wa, int add_same,
-                          int dtype, int out_f32, void* workspace, size_t workspace_bytes, const uint8_t* rowocc, void* stream);
 
 // dtype: 0 = bf16 activations/weights (fp32 accumulate), 1 = fp32 (exact-f32 MFMA).  out_f32: bf16 inputs, fp32 output.
 // transposed = 0: out[b,o,:] = sum_d in[b, o*stride - pad + d, :] . W[:, d, :]           (forward)
@@ -2283,8 +2264,8 @@ size_t dreg_conv3d_igemm_workspace_bytes(int B, int Di, int Hi, int Wi, int Cin,
     if (dtype != 0) return 0;
     ConvGeom g;
     if (fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, transposed, 2)) return 0;
-    const int s = conv_ksplit(g, has_addend != 0);
-    return s > 1 ? (size_t)s * g.M * Cout * sizeof(float) : 0;
+    const IgemmChoice c = igemm_choose(g, g.M, false, true, has_addend != 0, 2, 2);
+    return c.ksplit > 1 ? (size_t)c.ksplit * g.M * Cout * sizeof(float) : 0;
 }
 int dreg_conv3d_igemm_ws(const void* in, const void* wt_packed, void* out, const float* bias, const void* addend,
                          int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
@@ -2320,7 +2301,6 @@ int dreg_conv3d_igemm_occ(const void* in, const void* wt_packed, void* out, cons
 // multiple of its row tile): *rows_per_chunk = 128 when the sums were written, 0 when not (the caller then runs the ordinary
 // BatchNorm, whose first pass re-reads the tensor).  Same output as dreg_conv3d_igemm_ws, bit for bit; the sums of a grid do not
 // depend on the tile shape the launch's size selects (every form adds a chunk's rows in one fixed order).
-DREG_KNOB(int, g_bn_stats_epilogue, 1);   // probe knob (include/dreg_nerf_probe.h)
 #ifdef DREG_PROBE
 void dreg_conv_set_bn_stats_epilogue(int on) { g_bn_stats_epilogue = on ? 1 : 0; }
 #endif
@@ -2335,13 +2315,8 @@ int dreg_conv3d_igemm_bnstats(const void* in, const void* wt_packed, void* out, 
     int rc = fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, 0, 2);
     if (rc) return rc;
     if (g.M == 0) return DREG_OK;
-    const IgemmChoice c = igemm_choose(g, g.M, false, workspace != nullptr, addend != nullptr, 2);
-    const int V = Do * Ho * Wo;
-    const bool emit = g_bn_stats_epilogue && bn_partial && c.kind == 0 && c.ksplit == 1 && V % c.bm == 0 && V % 128 == 0 && ((c.bm == 128 && c.bn <= 128) || (c.bm == 256 && c.bn == 256));   // (LDS behind the 128 x 256 tile is too small for the class sums)
-    rc = launch_conv<bf16_t, bf16_t>(in, wt_packed, out, bias, addend, g, relu, Da, Ha, Wa, add_same ? 0 : 1, (hipStream_t)stream, nullptr, 0,
-                                     (float*)workspace, workspace_bytes, nullptr, emit ? bn_partial : nullptr);
-    if (rc == DREG_OK && emit) *rows_per_chunk = 128;     // every tile shape writes 128-row chunk sums in one canonical order
-    return rc;
+    return launch_conv<bf16_t, bf16_t>(in, wt_packed, out, bias, addend, g, relu, Da, Ha, Wa, add_same ? 0 : 1, (hipStream_t)stream, nullptr, 0,
+                                       (float*)workspace, workspace_bytes, nullptr, bn_partial, rows_per_chunk);
 }
 int dreg_conv3d_igemm(const void* in, const void* wt_packed, void* out, const float* bias, const void* addend,
                       int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
@@ -2352,12 +2327,13 @@ int dreg_conv3d_igemm(const void* in, const void* wt_packed, void* out, const fl
                                 Da, Ha, Wa, add_same, dtype, out_f32, nullptr, 0, stream);
 }
 
-static thread_local bool g_s2_accumulate_call = false;   // set by dreg_conv3d_dgrad_s2_acc around its call of dreg_conv3d_dgrad_s2
 // Data gradient of a stride-2 convolution (ksz 3 / pad 1 or ksz 1 / pad 0; bf16) without the 7/8 structurally-zero taps of the
 // gather form: one 2^3-tap convolution over dOut [B,Do,Ho,Wo,Cout] whose 8 x Cin output channels are the 8 parity classes
 // of dIn [B,Di,Hi,Wi,Cin] (written in place by the epilogue).  wt_class_packed: dreg_pack_conv_weight(..., for_dgrad = 2).
-int dreg_conv3d_dgrad_s2(const void* gout, const void* wt_class_packed, void* din, int B, int Di, int Hi, int Wi, int Cin,
-                         int Do, int Ho, int Wo, int Cout, int ksz, int pad, void* stream)
+// accumulate: ADDED to an existing dIn (a tensor with a second gradient contribution): in fp32 in the epilogue, one rounding; a 1^3 layer
+// touches the even-coordinate voxels only (the others keep their value: no fill).
+static int dgrad_s2(const void* gout, const void* wt_class_packed, void* din, int B, int Di, int Hi, int Wi, int Cin,
+                    int Do, int Ho, int Wo, int Cout, int ksz, int pad, bool accumulate, void* stream)
 {
     if (!g_use_glds) return DREG_EINVAL;   // served by the direct-to-LDS kernel only (callers check dreg_conv_get_glds)
     if (!((ksz == 3 && pad == 1) || (ksz == 1 && pad == 0)) || Cout % 64 != 0 || Cin % 8 != 0) return DREG_EINVAL;
@@ -2371,18 +2347,18 @@ int dreg_conv3d_dgrad_s2(const void* gout, const void* wt_class_packed, void* di
     int rc = fill_geom(g, B, Do, Ho, Wo, Cout, Dc, Hc, Wc, ncls * Cin, ksz == 1 ? 1 : 2, 1, 0, 0, 2);
     if (rc) return rc;
     if (g.M == 0) return DREG_OK;
-    if (ksz == 1 && !g_s2_accumulate_call && dreg_fill_zero(din, (size_t)B * Di * Hi * Wi * Cin * 2, st) != DREG_OK) return DREG_ELAUNCH;   // (own fill kernel: HBM rate; hipMemsetAsync's runs 256 workgroups)
-    return launch_conv<bf16_t, bf16_t>(gout, wt_class_packed, din, nullptr, g_s2_accumulate_call ? (const bf16_t*)din : nullptr, g, 0, Di, Hi, Wi, -Cin, st);
+    if (ksz == 1 && !accumulate && dreg_fill_zero(din, (size_t)B * Di * Hi * Wi * Cin * 2, st) != DREG_OK) return DREG_ELAUNCH;   // (own fill kernel: HBM rate; hipMemsetAsync's runs 256 workgroups)
+    return launch_conv<bf16_t, bf16_t>(gout, wt_class_packed, din, nullptr, accumulate ? (const bf16_t*)din : nullptr, g, 0, Di, Hi, Wi, -Cin, st);
 }
-// The same ADDED to an existing dIn (a tensor with a second gradient contribution): in fp32 in the epilogue, one rounding; a 1^3 layer
-// touches the even-coordinate voxels only (the others keep their value: no fill).
+int dreg_conv3d_dgrad_s2(const void* gout, const void* wt_class_packed, void* din, int B, int Di, int Hi, int Wi, int Cin,
+                         int Do, int Ho, int Wo, int Cout, int ksz, int pad, void* stream)
+{
+    return dgrad_s2(gout, wt_class_packed, din, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, pad, false, stream);
+}
 int dreg_conv3d_dgrad_s2_acc(const void* gout, const void* wt_class_packed, void* din, int B, int Di, int Hi, int Wi, int Cin,
                              int Do, int Ho, int Wo, int Cout, int ksz, int pad, void* stream)
 {
-    g_s2_accumulate_call = true;
-    const int rc = dreg_conv3d_dgrad_s2(gout, wt_class_packed, din, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, pad, stream);
-    g_s2_accumulate_call = false;
-    return rc;
+    return dgrad_s2(gout, wt_class_packed, din, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, pad, true, stream);
 }
 
 // 1 (default): bf16 stride-1 convolutions use the direct-to-LDS kernel (8-wave 256x256 tile when Cout % 256 == 0 and the row
@@ -2405,7 +2381,7 @@ int dreg_conv3d_igemm_defer(const void* in, const void* wt_packed, void* out, co
     if (g.M == 0) return DREG_OK;
     const SplitkDefer d{sk_nsplit, sk_slice};
     return launch_conv<bf16_t, bf16_t>(in, wt_packed, out, bias, addend, g, relu, Da, Ha, Wa, add_same ? 0 : 1, (hipStream_t)stream, nullptr, 0,
-                                       (float*)workspace, workspace_bytes, rowocc, nullptr, &d);
+                                       (float*)workspace, workspace_bytes, rowocc, nullptr, nullptr, &d);
 }
 #ifdef DREG_PROBE
 void dreg_conv_set_glds(int enable) { g_use_glds = enable; }
@@ -2426,7 +2402,7 @@ int dreg_conv1_bnrelu_a_probe(const void* in, const void* wt_packed, void* out, 
 #endif
 // measurement only: enable = 1 routes bf16 launches with Cout % 128 == 0 to the instrumented 128 x 128 kernel; read returns
 // { cycles waiting for the stage's loads, in the barrier, issuing the next stage, in fragment reads + MFMAs; K steps x waves; waves } and clears them
-// Which kernel a convolution launch of this shape runs (the rules launch_conv applies; for profiler labels):
+// Which kernel a convolution launch of this shape runs (igemm_choose, the choice launch_conv launches from; for profiler labels; bf16 output assumed):
 //   kind * 100000000 + BM * 100000 + BN * 100 + AP * 10 + (split-K ? 1 : 0);   kind 0 = conv_igemm_glds_kernel, 1 = conv_igemm_kernel, negative = unsupported.
 // nrows: 0 = dense, else the row-list length; has_ws: the caller passes a split-K workspace (dreg_conv3d_igemm_ws); dtype 0 bf16, 1 fp32.
 int dreg_conv3d_igemm_variant(int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int ksz, int stride, int pad,
@@ -2434,7 +2410,7 @@ int dreg_conv3d_igemm_variant(int B, int Di, int Hi, int Wi, int Cin, int Do, in
 {
     ConvGeom g;
     if (fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, transposed, dtype == 0 ? 2 : 4)) return -1;
-    const IgemmChoice c = igemm_choose(g, nrows > 0 ? (uint32_t)nrows : g.M, nrows > 0, has_ws != 0, has_addend != 0, dtype == 0 ? 2 : 4);
+    const IgemmChoice c = igemm_choose(g, nrows > 0 ? (uint32_t)nrows : g.M, nrows > 0, has_ws != 0, has_addend != 0, dtype == 0 ? 2 : 4, dtype == 0 ? 2 : 4);
     if (c.kind < 0) return -1;
     return c.kind * 100000000 + c.bm * 100000 + c.bn * 100 + c.ap * 10 + (c.ksplit > 1 ? 1 : 0);
 }
@@ -2466,10 +2442,7 @@ void dreg_conv_set_wgrad_pipe(int enable) { g_wgrad_pipe = enable ? 1 : 0; }
 int dreg_conv_get_glds(void) { return g_use_glds; }
 
 // K padding of the packed weight row for (ntaps, Cin) at dtype.
-int dreg_conv3d_kpad(int ksz, int Cin, int dtype) {
-    const int bke = dtype == 0 ? 64 : 32;
-    return ((ksz * ksz * ksz * Cin + bke - 1) / bke) * bke;
-}
+int dreg_conv3d_kpad(int ksz, int Cin, int dtype) { return conv_kpad(ksz, Cin, dtype == 0 ? 2 : 4); }
 
 int dreg_pack_conv_weight(const float* w, void* out, int Cout, int Cin_real, int Cin, int ksz, int for_dgrad,
                           int dtype, void* stream)
@@ -2543,9 +2516,7 @@ int dreg_conv3d_wgrad_splits(int B, int Do, int Ho, int Wo, int Cin, int Cout, i
         if (f > (Mf + 63) / 64) f = (Mf + 63) / 64;
         return (int)(f > 64 ? 64 : (f < 1 ? 1 : f));
     }
-    const int es = dtype == 0 ? 2 : 4;
-    const int bke = 128 / es;
-    const int Kpad = ((ksz * ksz * ksz * Cin + bke - 1) / bke) * bke;
+    const int Kpad = dreg_conv3d_kpad(ksz, Cin, dtype);
     const int bnc = (Kpad % 128 == 0 || (dtype == 0 && Kpad > 128)) ? 128 : 64;
     const long tiles = (long)((Cout % 128 == 0) ? Cout / 128 : Cout / 64) * ((Kpad + bnc - 1) / bnc);
     const long M = (long)B * Do * Ho * Wo;
@@ -2579,9 +2550,7 @@ int dreg_conv3d_wgrad_splits(int B, int Do, int Ho, int Wo, int Cin, int Cout, i
     return (int)s;
 }
 size_t dreg_conv3d_wgrad_workspace_bytes(int B, int Do, int Ho, int Wo, int Cin, int Cout, int ksz, int dtype) {
-    const int es = dtype == 0 ? 2 : 4;
-    const int bke = 128 / es;
-    const int Kpad = ((ksz * ksz * ksz * Cin + bke - 1) / bke) * bke;
+    const int Kpad = dreg_conv3d_kpad(ksz, Cin, dtype);
     // + 256: one int behind the slices, the number of slices a row-list launch actually wrote (see wgrad_row_splits)
     return (size_t)dreg_conv3d_wgrad_splits(B, Do, Ho, Wo, Cin, Cout, ksz, dtype) * Cout * Kpad * sizeof(float) + 256;
 }
@@ -2622,6 +2591,137 @@ static int wgrad_row_splits(int Cout, int Kpad, int ksz, uint32_t nrows, int sma
     return (int)(s < smax ? s : smax);
 }
 
+}  // extern "C"
+
+// Which weight-gradient kernel instantiation a launch runs, and with which launch arguments.  ONE rule set: wgrad_impl launches from it,
+// dreg_conv3d_wgrad_group_fill copies its descriptor fields from it and dreg_conv3d_wgrad_variant encodes it for the profiler's labels.
+enum WgradFamily {
+    WG_UNSUPPORTED = -1,       // (a row-list slice that does not fit in LDS: the caller falls back to dense)
+    WG_REG,                    // conv_wgrad_kernel<T, bm, bnc, use_tr>: register-staged (fp32, use_tr = 0, glds off, an operand >= 2 GiB)
+    WG_GLDS4,                  // conv_wgrad_glds_kernel<bm, bnc, rowlist, 4>: the four-wave direct-to-LDS tiles (the only family a grouped launch takes)
+    WG_256x128,                // conv_wgrad_glds_kernel<256, 128, false, 4, 0, 32>: g_wgrad_big = 1
+    WG_DENSE8,                 // conv_wgrad_glds_kernel<256, 256, false, 8, abl, kv, ns, pipe, ap>: large dense layers, the form picked by the ring / pipe / ablation knobs
+    WG_ROWS8,                  // conv_wgrad_glds_kernel<256, 256, true, 8>: row lists of >= 65,536 rows, lockstep
+    WG_ROWS8_AP                // conv_wgrad_glds_kernel<256, 256, true, 8, 0, 32, 4, 0, 3>: row lists of >= 16,384 rows, anti-phase wave groups
+};
+struct WgradChoice {
+    WgradFamily family;
+    int bm, bnc, tilesRow, tilesCol;       // weight tile and tile counts over Cout x Kpad
+    int smax, nsplit;                      // slices the workspace is sized for / slices this launch writes (row lists: nsplit <= smax)
+    uint32_t vps;                          // voxels (rows) per split
+    int rows_fast;                         // row lists: 8 bytes per row in LDS (index + packed coordinates)
+    bool occ;                              // the occupancy flags are honoured (per output W-row: stages must not straddle rows)
+    int abl, kv, ns, pipe, ap;             // WG_DENSE8: the remaining template arguments
+    uint64_t gbytes, ibytes;               // operand sizes (bf16)
+    dim3 grid; int block; size_t lds;
+};
+static WgradChoice wgrad_choose(const ConvGeom& g, int dtype, bool use_tr, bool rowlist, uint32_t nrows_list, bool occ)
+{
+    WgradChoice c{};
+    const int Cout = g.Cout, Kpad = g.Kpad, es = dtype == 0 ? 2 : 4;
+    const uint32_t nrows = rowlist ? nrows_list : g.M;
+    c.smax = dreg_conv3d_wgrad_splits(g.B, g.Do, g.Ho, g.Wo, g.Cin, Cout, g.ksz, dtype);
+    // row lists over a stride-1 same-size volume (what the active-set head launches)
+    const bool same_vol = g.sn == 1 && g.sd == 1 && g.dsign == 1 && g.Di == g.Do && g.Hi == g.Ho && g.Wi == g.Wo && g.Do < 1024 && g.Ho < 1024 && g.Wo < 1024;
+    const bool k256 = Cout % 256 == 0 && (Kpad % 256 == 0 || Kpad >= 1024);    // 256 x 256 weight tiles (a K extent that is not a multiple of 256 — 27 taps
+                                                                               // x 64 channels = 1,728 — takes a ragged last column tile: its columns >= Kpad gather zeros and are not stored)
+    // anti-phase wave groups on the row list ((row, border flags) pairs in LDS; lean load half as in the dense form): lists of >= 16,384 rows
+    // (the 32^3 level of the active-set head: 28 k rows ran at 0.26 PFLOP/s on the four-wave tile)
+    const bool rows_ap = rowlist && same_vol && g_rows_fast && g_wgrad_big == 3 && g_wgrad_ring == 3 && g.ksz <= 3 && k256 && nrows >= 16384;
+    c.nsplit = rowlist ? wgrad_row_splits(Cout, Kpad, g.ksz, nrows, c.smax, rows_ap) : c.smax;
+    c.vps = (uint32_t)((nrows + c.nsplit - 1) / c.nsplit);
+    c.vps = ((c.vps + 63) / 64) * 64;
+    if (c.vps == 0) c.vps = 64;
+    c.gbytes = (uint64_t)g.M * Cout * 2; c.ibytes = (uint64_t)g.B * g.Di * g.Hi * g.Wi * g.Cin * 2;
+    const bool glds = dtype == 0 && use_tr && g_use_glds && c.gbytes < 0x7fffff00ull && c.ibytes < 0x7fffff00ull;
+    c.bm = (Cout % 128 == 0) ? 128 : 64;
+    // 128 columns per tile also when Kpad is an odd multiple of 64 (3^3 taps x 64 channels = 1,728): the direct-to-LDS kernel
+    // masks the ragged last tile (columns >= Kpad gather zeros and are not stored); the older kernels need exact tiles
+    c.bnc = (Kpad % 128 == 0 || (glds && Kpad > 128)) ? 128 : 64;
+    // launches that leave most CUs empty (the point-set half's linear layers: 4 weight tiles x 16 splits) take 64-wide tiles: up to
+    // four times the workgroups, the same per-element accumulation order
+    if (g_narrow_small >= 2 && dtype == 0 && (Cout / c.bm) * ((Kpad + c.bnc - 1) / c.bnc) * c.nsplit < g_narrow_thr) {
+        if (c.bnc == 128) c.bnc = 64;
+        if (c.bm == 128 && (Cout / c.bm) * (Kpad / c.bnc) * c.nsplit < g_narrow_thr) c.bm = 64;
+    }
+    c.occ = occ && !rowlist && g.Wo % 64 == 0;
+    c.kv = 64; c.ns = 2; c.block = 256;
+    size_t lds_rows = 0;                   // LDS behind the stages: the split's slice of the row list, or its occupancy flags
+    if (!glds) c.family = WG_REG;
+    else if (rowlist && c.vps > 20480) { c.family = WG_UNSUPPORTED; return c; }     // the row-list slice must fit in LDS behind the stages
+    else if (rows_ap && (size_t)4 * 32 * 512 * 2 + ((size_t)c.vps + 5 * 32) * 8 <= (size_t)160 * 1024) {
+        c.family = WG_ROWS8_AP; c.kv = 32; c.ns = 4; c.ap = 3; c.rows_fast = 1; lds_rows = ((size_t)c.vps + 5 * 32) * 8;
+    } else if (rowlist && same_vol && g_rows_fast && g_wgrad_big == 3 && Cout % 256 == 0 && Kpad % 256 == 0 && nrows >= 65536 &&
+               (size_t)2 * 64 * 512 * 2 + (size_t)c.vps * 8 <= (size_t)160 * 1024) {
+        c.family = WG_ROWS8; c.rows_fast = 1; lds_rows = (size_t)c.vps * 8;
+    } else if (!rowlist && !c.occ && g_wgrad_big && Cout % 256 == 0 && (Kpad % 256 == 0 || (Kpad >= 1024 && g_wgrad_big == 3 && g_wgrad_ring >= 3 && !g_wgrad_pipe)) && nrows >= 65536) {
+        // large dense layers: 256-row tiles.  Default (3): the 8-wave 256 x 256 tile (0.90 PFLOP/s on 256 -> 256 @64^3 alone); 1: 4
+        // waves on 256 x 128 with 32-voxel stages — 48 KB of LDS, two independent workgroups per CU: 0.93 alone, but no faster
+        // inside the step, where the data-gradient stream shares the CUs (tools/ab_step.py: 43.25 vs 43.16 ms, dense head)
+        c.family = WG_DENSE8;
+        if (g_wgrad_big == 1) { c.family = WG_256x128; c.kv = 32; }
+        else if (g_wgrad_big >= 11 && g_wgrad_big <= 13) c.abl = g_wgrad_big - 10;      // ablations of the 8-wave kernel
+        else if (g_wgrad_pipe && !g_wgrad_ring) c.pipe = 1;
+        else if (g_wgrad_ring == 2) { c.kv = 32; c.ns = 5; }                            // five 32-voxel stages: the whole 160 KB of LDS, four stages in flight
+        else if (g_wgrad_ring >= 3 && g_wgrad_ring <= 8) {
+            // anti-phase wave groups over a ring of four 32-voxel units.  3: product form (FAST when the layer qualifies, else the general
+            // loop); 8: the general loop; 4..7 measurement only: FAST with s_memtime stamps, 5..7 (wrong results) without fragment
+            // reads / without pieces / without MFMAs
+            const bool fast_ok = g.ksz <= 3 && g.sn == 1 && g.sd == 1 && g.dsign == 1 && g.Di == g.Do && g.Hi == g.Ho && g.Wi == g.Wo && (g.Wo % 32) == 0 &&
+                                 (g.M % 32u) == 0 && (c.vps % 32u) == 0;
+            c.kv = 32; c.ns = 4;
+            if (g_wgrad_ring == 8 || !fast_ok) c.ap = 1;
+            else if (g_wgrad_ring == 3) c.ap = 3;
+            else { c.ap = 4; c.abl = g_wgrad_ring == 5 ? 2 : (g_wgrad_ring == 6 ? 3 : (g_wgrad_ring == 7 ? 1 : 0)); }
+        } else if (g_wgrad_ring == 1) { c.kv = 32; c.ns = 4; }
+    } else {
+        c.family = WG_GLDS4;
+        if (rowlist) {
+            c.rows_fast = (same_vol && g_rows_fast && (size_t)2 * 64 * (c.bm + c.bnc) * 2 + (size_t)c.vps * 8 <= (size_t)160 * 1024) ? 1 : 0;
+            lds_rows = (size_t)c.vps * (c.rows_fast ? 8 : 4);
+        } else if (c.occ) lds_rows = (size_t)(c.vps / 64 + 16);
+    }
+    if (c.family == WG_256x128) { c.bm = 256; c.bnc = 128; }
+    else if (c.family >= WG_DENSE8) { c.bm = 256; c.bnc = 256; c.block = 512; }
+    c.tilesRow = Cout / c.bm; c.tilesCol = (Kpad + c.bnc - 1) / c.bnc;
+    if (c.family == WG_REG) { c.grid = dim3(c.tilesRow * c.tilesCol, c.nsplit); c.lds = (size_t)2 * 32 * (c.bm + c.bnc) * es; }
+    else { c.grid = dim3(c.tilesRow * c.tilesCol * c.nsplit); c.lds = (size_t)c.ns * c.kv * (c.bm + c.bnc) * 2 + lds_rows; }
+    return c;
+}
+
+struct WgradArgs { const void *gout, *in; float* part; const int* rowlist; uint32_t nrows; const uint8_t* rowocc; };
+template <typename T, bool TR>
+static void wgrad_reg_launch(const WgradChoice& c, const ConvGeom& g, const WgradArgs& a, hipStream_t st)
+{
+#define WG_LAUNCH(BMv, BNv) hipLaunchKernelGGL((conv_wgrad_kernel<T, BMv, BNv, TR>), c.grid, dim3(c.block), c.lds, st, (const T*)a.gout, (const T*)a.in, a.part, g, c.tilesCol, c.vps, a.rowocc)
+    if (c.bm == 128 && c.bnc == 128) WG_LAUNCH(128, 128); else if (c.bm == 128) WG_LAUNCH(128, 64);
+    else if (c.bnc == 128) WG_LAUNCH(64, 128); else WG_LAUNCH(64, 64);
+#undef WG_LAUNCH
+}
+template <int BM, int BNC, bool ROWS, int NW = 4, int ABL = 0, int KV = 64, int NS = 2, int PIPE = 0, int AP = 0>
+static void wgrad_glds_launch(const WgradChoice& c, const ConvGeom& g, const WgradArgs& a, hipStream_t st)
+{
+    if (c.lds > 65536) (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<BM, BNC, ROWS, NW, ABL, KV, NS, PIPE, AP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);
+    hipLaunchKernelGGL((conv_wgrad_glds_kernel<BM, BNC, ROWS, NW, ABL, KV, NS, PIPE, AP>), c.grid, dim3(c.block), c.lds, st, (const bf16_t*)a.gout, (const bf16_t*)a.in, a.part, g,
+                       c.tilesCol, c.tilesRow * c.tilesCol, c.nsplit, c.vps, (uint32_t)c.gbytes, (uint32_t)c.ibytes, a.rowlist, a.nrows, a.rowocc, c.rows_fast);
+}
+template <bool ROWS>
+static void wgrad_glds4_launch(const WgradChoice& c, const ConvGeom& g, const WgradArgs& a, hipStream_t st)
+{
+    if (c.bm == 128 && c.bnc == 128) wgrad_glds_launch<128, 128, ROWS>(c, g, a, st); else if (c.bm == 128) wgrad_glds_launch<128, 64, ROWS>(c, g, a, st);
+    else if (c.bnc == 128) wgrad_glds_launch<64, 128, ROWS>(c, g, a, st); else wgrad_glds_launch<64, 64, ROWS>(c, g, a, st);
+}
+// the dense 8-wave instantiations that exist, by the choice's template arguments
+static void wgrad_dense8_launch(const WgradChoice& c, const ConvGeom& g, const WgradArgs& a, hipStream_t st)
+{
+#define D8(A, KVv, NSv, PPv, APv) if (c.abl == A && c.kv == KVv && c.ns == NSv && c.pipe == PPv && c.ap == APv) return wgrad_glds_launch<256, 256, false, 8, A, KVv, NSv, PPv, APv>(c, g, a, st)
+    D8(0, 32, 4, 0, 3); D8(0, 32, 4, 0, 1);                                          // anti-phase: the FAST form, the general loop
+    D8(0, 64, 2, 0, 0); D8(0, 32, 4, 0, 0); D8(0, 32, 5, 0, 0); D8(0, 64, 2, 1, 0);    // lockstep rings of 2 / 4 / 5 stages; fragments read one MFMA group ahead
+    D8(1, 64, 2, 0, 0); D8(2, 64, 2, 0, 0); D8(3, 64, 2, 0, 0);                        // ablations of the lockstep kernel
+    D8(0, 32, 4, 0, 4); D8(1, 32, 4, 0, 4); D8(2, 32, 4, 0, 4); D8(3, 32, 4, 0, 4);    // measurement forms of the anti-phase kernel
+#undef D8
+}
+
 // dW[Cout][Cin_real][ntaps] (torch layout, fp32) (+)= sum_m gout[m][:]^T x gathered in[m][tap][:]
 // gout: [B,Do,Ho,Wo,Cout], in: [B,Di,Hi,Wi,Cin] (same dtype).  use_tr: 1 = LDS transpose reads (bf16 only).
 static int wgrad_impl(const void* gout, const void* in, float* dw, void* workspace, size_t workspace_bytes,
@@ -2630,159 +2730,42 @@ static int wgrad_impl(const void* gout, const void* in, float* dw, void* workspa
                       const int* rowlist, uint32_t nrows_list, const uint8_t* rowocc = nullptr, bool defer_reduce = false)
 {
     ConvGeom g;
-    const int es = dtype == 0 ? 2 : 4;
-    int rc = fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, 0, es);
+    int rc = fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, 0, dtype == 0 ? 2 : 4);
     if (rc) return rc;
     if (Cout % 128 != 0 && Cout != 64) return DREG_EINVAL;
     if (workspace_bytes < dreg_conv3d_wgrad_workspace_bytes(B, Do, Ho, Wo, Cin, Cout, ksz, dtype)) return DREG_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t nrows = rowlist ? nrows_list : g.M;
     if (rowlist && !(dtype == 0 && use_tr && g_use_glds)) return DREG_EINVAL;
-    const int smax = dreg_conv3d_wgrad_splits(B, Do, Ho, Wo, Cin, Cout, ksz, dtype);
-    const bool row_tile256 = rowlist && g.sn == 1 && g.sd == 1 && g.dsign == 1 && Di == Do && Hi == Ho && Wi == Wo && Do < 1024 && Ho < 1024 && Wo < 1024 &&
-                             g_rows_fast && g_wgrad_big == 3 && g_wgrad_ring == 3 && ksz <= 3 && Cout % 256 == 0 && (g.Kpad % 256 == 0 || g.Kpad >= 1024) && nrows >= 16384;
-    const int nsplit = rowlist ? wgrad_row_splits(Cout, g.Kpad, ksz, nrows, smax, row_tile256) : smax;
-    uint32_t vps = (uint32_t)((nrows + nsplit - 1) / nsplit);
-    vps = ((vps + 63) / 64) * 64;
-    if (vps == 0) vps = 64;
-    int bm = (Cout % 128 == 0) ? 128 : 64;
-    const uint64_t gbytes = (uint64_t)g.M * Cout * 2, ibytes = (uint64_t)B * Di * Hi * Wi * Cin * 2;
-    const bool glds_path = dtype == 0 && use_tr && g_use_glds && gbytes < 0x7fffff00ull && ibytes < 0x7fffff00ull;
-    // 128 columns per tile also when Kpad is an odd multiple of 64 (3^3 taps x 64 channels = 1,728): the direct-to-LDS kernel
-    // masks the ragged last tile (columns >= Kpad gather zeros and are not stored); the older kernels need exact tiles
-    int bnc = (g.Kpad % 128 == 0 || (glds_path && g.Kpad > 128)) ? 128 : 64;
-    // launches that leave most CUs empty (the point-set half's linear layers: 4 weight tiles x 16 splits) take 64-wide tiles: up to
-    // four times the workgroups, the same per-element accumulation order
-    if (g_narrow_small >= 2 && dtype == 0 && (Cout / bm) * ((g.Kpad + bnc - 1) / bnc) * nsplit < g_narrow_thr) {
-        if (bnc == 128) bnc = 64;
-        if (bm == 128 && (Cout / bm) * (g.Kpad / bnc) * nsplit < g_narrow_thr) bm = 64;
-    }
-    const int tilesRow = Cout / bm;
-    const int tilesCol = (g.Kpad + bnc - 1) / bnc;
-    dim3 grid(tilesRow * tilesCol, nsplit);
-    const size_t lds = (size_t)2 * 32 * (bm + bnc) * es;
+    hipStream_t st = (hipStream_t)stream;
+    const WgradChoice c = wgrad_choose(g, dtype, use_tr != 0, rowlist != nullptr, nrows_list, rowocc != nullptr);
     float* part = (float*)workspace;
-    if (rowocc && (rowlist || Wo % 64 != 0)) rowocc = nullptr;   // the flags are per output W-row: stages must not straddle rows
-#define WG_LAUNCH(T, BMv, BNv, TRv) hipLaunchKernelGGL((conv_wgrad_kernel<T, BMv, BNv, TRv>), grid, dim3(256), lds, st, (const T*)gout, (const T*)in, part, g, tilesCol, vps, rowocc)
-#define WG_DISPATCH(T, TRv) do { \
-        if (bm == 128 && bnc == 128) WG_LAUNCH(T, 128, 128, TRv); \
-        else if (bm == 128 && bnc == 64) WG_LAUNCH(T, 128, 64, TRv); \
-        else if (bm == 64 && bnc == 128) WG_LAUNCH(T, 64, 128, TRv); \
-        else WG_LAUNCH(T, 64, 64, TRv); } while (0)
-    if (glds_path) {
-#define WGG_(BMv, BNv, KVv, NSv, PPv) do { if (rowlist) hipLaunchKernelGGL((conv_wgrad_glds_kernel<BMv, BNv, true, 4, 0, KVv, NSv, PPv>), dim3(tilesRow * tilesCol * nsplit), dim3(256), (size_t)2 * 64 * (bm + bnc) * 2 + (size_t)vps * (rows_fast ? 8 : 4), st, (const bf16_t*)gout, (const bf16_t*)in, part, g, tilesCol, tilesRow * tilesCol, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr, rows_fast); \
-        else hipLaunchKernelGGL((conv_wgrad_glds_kernel<BMv, BNv, false, 4, 0, KVv, NSv, PPv>), dim3(tilesRow * tilesCol * nsplit), dim3(256), (size_t)2 * 64 * (bm + bnc) * 2 + (rowocc ? (size_t)(vps / KVv + 16) : 0), st, (const bf16_t*)gout, (const bf16_t*)in, part, g, tilesCol, tilesRow * tilesCol, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, rowocc); } while (0)
-#define WGG(BMv, BNv) WGG_(BMv, BNv, 64, 2, 0)
-        if (rowlist && vps > 20480) return DREG_EINVAL;   // the row-list slice must fit in LDS behind the stages (caller falls back to dense)
-        // row lists over a stride-1 same-size volume (what the active-set head launches): 8 bytes per row in LDS (index + packed
-        // coordinates) when that fits, and the 8-wave 256 x 256 tile for the 256 -> 256 layers
-        const bool same_vol = g.sn == 1 && g.sd == 1 && g.dsign == 1 && Di == Do && Hi == Ho && Wi == Wo && Do < 1024 && Ho < 1024 && Wo < 1024;
-        const bool rows256 = rowlist && same_vol && g_rows_fast && g_wgrad_big == 3 && Cout % 256 == 0 && g.Kpad % 256 == 0 && nrows >= 65536 &&
-                             (size_t)2 * 64 * 512 * 2 + (size_t)vps * 8 <= (size_t)160 * 1024;
-        const int rows_fast = (rowlist && same_vol && g_rows_fast && (rows256 || (size_t)2 * 64 * (bm + bnc) * 2 + (size_t)vps * 8 <= (size_t)160 * 1024)) ? 1 : 0;
-        if (rowlist) {
-            const int ldsr = 2 * 64 * (bm + bnc) * 2 + (int)vps * 4;
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<128, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<128, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<64, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<64, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-
-            (void)ldsr;
-        }
-        // anti-phase wave groups on the row list ((row, border flags) pairs in LDS; lean load half as in the dense form).  Also for
-        // lists of >= 16,384 rows (the 32^3 level of the active-set head: 28 k rows ran at 0.26 PFLOP/s on the four-wave tile) and for a K
-        // extent that is not a multiple of 256 (27 taps x 64 channels: ragged last column tile, as in the dense form)
-        const bool rows256_ap = rowlist && same_vol && g_rows_fast && g_wgrad_big == 3 && g_wgrad_ring == 3 && ksz <= 3 && Cout % 256 == 0 &&
-                                (g.Kpad % 256 == 0 || g.Kpad >= 1024) && nrows >= 16384 &&
-                                (size_t)4 * 32 * 512 * 2 + ((size_t)vps + 5 * 32) * 8 <= (size_t)160 * 1024;
-        if (rows256_ap) {
-            const int tiles256 = (Cout / 256) * ((g.Kpad + 255) / 256);
-            const size_t l_ = (size_t)4 * 32 * 512 * 2 + ((size_t)vps + 5 * 32) * 8;
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, true, 8, 0, 32, 4, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, true, 8, 0, 32, 4, 0, 3>), dim3(tiles256 * nsplit), dim3(512), l_, st, (const bf16_t*)gout,
-                               (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr, 1);
-        } else
-        if (rows256) {
-            const int tiles256 = (Cout / 256) * (g.Kpad / 256);
-            const size_t l_ = (size_t)2 * 64 * 512 * 2 + (size_t)vps * 8;
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, true, 8>), dim3(tiles256 * nsplit), dim3(512), l_, st, (const bf16_t*)gout,
-                               (const bf16_t*)in, part, g, g.Kpad / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr, 1);
-        } else
-        // (a K extent that is not a multiple of 256 — 27 taps x 64 channels = 1,728 — takes a ragged last column tile: its columns >= Kpad
-        //  gather zeros and are not stored)
-        if (!rowlist && !rowocc && g_wgrad_big && Cout % 256 == 0 && (g.Kpad % 256 == 0 || (g.Kpad >= 1024 && g_wgrad_big == 3 && g_wgrad_ring >= 3 && !g_wgrad_pipe)) && nrows >= 65536) {
-            // large dense layers: 256-row tiles.  Default (3): the 8-wave 256 x 256 tile (0.90 PFLOP/s on 256 -> 256 @64^3 alone); 1: 4
-            // waves on 256 x 128 with 32-voxel stages — 48 KB of LDS, two independent workgroups per CU: 0.93 alone, but no faster
-            // inside the step, where the data-gradient stream shares the CUs (tools/ab_step.py: 43.25 vs 43.16 ms, dense head)
-            // large dense layers: the 8-wave 256 x 256 tile
-            const int tiles256 = (Cout / 256) * ((g.Kpad + 255) / 256);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 512 * 2);
-            if (g_wgrad_big == 1) {
-                const int t2 = (Cout / 256) * (g.Kpad / 128);
-                const size_t l_ = (size_t)2 * 32 * 384 * 2;
-                uint32_t vps2 = ((vps + 31) / 32) * 32;
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 128, false, 4, 0, 32>), dim3(t2 * nsplit), dim3(256), l_, st, (const bf16_t*)gout,
-                                   (const bf16_t*)in, part, g, g.Kpad / 128, t2, nsplit, vps2, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr);
-            } else if (g_wgrad_big >= 11 && g_wgrad_big <= 13) {   // ablations of the 8-wave kernel
-                const size_t l_ = (size_t)2 * 64 * 512 * 2;
-#define WG_ABL(A) do { (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l_); \
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8, A>), dim3(tiles256 * nsplit), dim3(512), l_, st, (const bf16_t*)gout, \
-                                   (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, rowocc); } while (0)
-                if (g_wgrad_big == 11) WG_ABL(1); else if (g_wgrad_big == 12) WG_ABL(2); else WG_ABL(3);
-#undef WG_ABL
-            } else if (g_wgrad_pipe && !g_wgrad_ring) {
-                (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8, 0, 64, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8, 0, 64, 2, 1>), dim3(tiles256 * nsplit), dim3(512), (size_t)2 * 64 * 512 * 2 + (rowocc ? (size_t)(vps / 64 + 16) : 0), st, (const bf16_t*)gout,
-                                   (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, rowocc);
-            } else if (g_wgrad_ring == 2) {   // five 32-voxel stages: the whole 160 KB of LDS, four stages in flight
-                (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8, 0, 32, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8, 0, 32, 5>), dim3(tiles256 * nsplit), dim3(512), (size_t)5 * 32 * 512 * 2, st, (const bf16_t*)gout,
-                                   (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr);
-            } else if (g_wgrad_ring >= 3 && g_wgrad_ring <= 8) {
-                // anti-phase wave groups over a ring of four 32-voxel units.  3: product form (FAST when the layer qualifies, else the general
-                // loop); 8: the general loop; 4..7 measurement only: FAST with s_memtime stamps, 5..7 (wrong results) without fragment
-                // reads / without pieces / without MFMAs
-                const bool fast_ok = ksz <= 3 && g.sn == 1 && g.sd == 1 && g.dsign == 1 && Di == Do && Hi == Ho && Wi == Wo && (Wo % 32) == 0 &&
-                                     (g.M % 32u) == 0 && (vps % 32u) == 0;
-#define WG_AP(A, APv) do { (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8, A, 32, 4, 0, APv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8, A, 32, 4, 0, APv>), dim3(tiles256 * nsplit), dim3(512), (size_t)4 * 32 * 512 * 2, st, (const bf16_t*)gout, \
-                                   (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr, 0); } while (0)
-                if (g_wgrad_ring == 8 || !fast_ok) WG_AP(0, 1);
-                else if (g_wgrad_ring == 3) WG_AP(0, 3);
-                else if (g_wgrad_ring == 4) WG_AP(0, 4);
-                else if (g_wgrad_ring == 5) WG_AP(2, 4);
-                else if (g_wgrad_ring == 6) WG_AP(3, 4);
-                else WG_AP(1, 4);
-#undef WG_AP
-            } else if (g_wgrad_ring == 1) {
-                (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<256, 256, false, 8, 0, 32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8, 0, 32, 4>), dim3(tiles256 * nsplit), dim3(512), (size_t)4 * 32 * 512 * 2, st, (const bf16_t*)gout,
-                                   (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, nullptr);
-            } else
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 256, false, 8>), dim3(tiles256 * nsplit), dim3(512), (size_t)2 * 64 * 512 * 2, st, (const bf16_t*)gout,
-                               (const bf16_t*)in, part, g, (g.Kpad + 255) / 256, tiles256, nsplit, vps, (uint32_t)gbytes, (uint32_t)ibytes, rowlist, nrows, rowocc);
-        } else
-        if (bm == 128 && bnc == 128) WGG(128, 128); else if (bm == 128 && bnc == 64) WGG(128, 64);
-        else if (bm == 64 && bnc == 128) WGG(64, 128); else WGG(64, 64);
-#undef WGG
-    } else
-    if (dtype == 0) { if (use_tr) WG_DISPATCH(bf16_t, true); else WG_DISPATCH(bf16_t, false); }
-    else WG_DISPATCH(float, false);
-#undef WG_DISPATCH
-#undef WG_LAUNCH
+    const WgradArgs a{gout, in, part, rowlist, rowlist ? nrows_list : g.M, c.occ ? rowocc : nullptr};
+    switch (c.family) {
+    case WG_UNSUPPORTED: return DREG_EINVAL;                // (caller falls back to dense)
+    case WG_REG:
+        if (dtype != 0) wgrad_reg_launch<float, false>(c, g, a, st);
+        else if (use_tr) wgrad_reg_launch<bf16_t, true>(c, g, a, st);
+        else wgrad_reg_launch<bf16_t, false>(c, g, a, st);
+        break;
+    case WG_GLDS4: if (rowlist) wgrad_glds4_launch<true>(c, g, a, st); else wgrad_glds4_launch<false>(c, g, a, st); break;
+    case WG_256x128: wgrad_glds_launch<256, 128, false, 4, 0, 32>(c, g, a, st); break;
+    case WG_DENSE8: wgrad_dense8_launch(c, g, a, st); break;
+    case WG_ROWS8: wgrad_glds_launch<256, 256, true, 8>(c, g, a, st); break;
+    case WG_ROWS8_AP: wgrad_glds_launch<256, 256, true, 8, 0, 32, 4, 0, 3>(c, g, a, st); break;
+    }
     DREG_LAUNCH_CHECK();
     if (defer_reduce) {                  // the caller sums the splits later (dreg_wgrad_reduce_batched)
         // row lists: how many slices were written, behind the slices (a 4-byte fill on the same stream)
-        if (rowlist && hipMemsetD32Async((hipDeviceptr_t)(part + (size_t)smax * Cout * g.Kpad), nsplit, 1, st) != hipSuccess) return DREG_ELAUNCH;
+        if (rowlist && hipMemsetD32Async((hipDeviceptr_t)(part + (size_t)c.smax * Cout * g.Kpad), c.nsplit, 1, st) != hipSuccess) return DREG_ELAUNCH;
         return DREG_OK;
     }
     if (g.ntaps > 1 && (size_t)g.ntaps * (Cin < 64 ? Cin : 64) > (size_t)WR_STAGE) return DREG_EINVAL;
-    WgradReduceDesc rd{part, dw, nsplit, Cout, g.Kpad, g.ntaps, Cin, Cin_real, accumulate, 0};
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_blocks(Cout, Cin_real, g.ntaps, nsplit)), dim3(256), 0, st, rd);
+    WgradReduceDesc rd{part, dw, c.nsplit, Cout, g.Kpad, g.ntaps, Cin, Cin_real, accumulate, 0};
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_blocks(Cout, Cin_real, g.ntaps, c.nsplit)), dim3(256), 0, st, rd);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
 }
+
+extern "C" {
 
 // ---- weight gradients of MANY linear layers in one launch per tile shape (see GRP above).
 // dreg_linear_wgrad_group_fill writes the 144-byte descriptor of y = x W^T (x: bf16 [rows, Cin], gout: bf16 [rows, Cout], split partials
@@ -2790,9 +2773,6 @@ static int wgrad_impl(const void* gout, const void* in, float* dw, void* workspa
 // and returns its tile shape (*variant = BM * 1000 + BNC) and workgroup count; block0 is left to the caller (exclusive prefix of the
 // workgroup counts inside one variant's table).  DREG_EINVAL: the layer does not take the four-wave direct-to-LDS kernel (caller falls back).
 int dreg_wgrad_group_desc_bytes() { return (int)sizeof(WgradGroupDesc); }
-int dreg_conv3d_wgrad_group_fill(void* desc_host, const void* gout, const void* in, void* workspace, size_t workspace_bytes,
-                                 int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int ksz, int stride, int pad,
-                                 int* variant, int* nblocks);
 int dreg_linear_wgrad_group_fill(void* desc_host, const void* gout, const void* in, void* workspace, size_t workspace_bytes,
                                  int rows, int Cin, int Cout, int* variant, int* nblocks)
 {
@@ -2807,30 +2787,17 @@ int dreg_conv3d_wgrad_group_fill(void* desc_host, const void* gout, const void* 
     ConvGeom g;
     int rc = fill_geom(g, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksz, stride, pad, 0, 2);
     if (rc) return rc;
-    if ((Cout % 128 != 0 && Cout != 64) || !g_use_glds) return DREG_EINVAL;
+    if (Cout % 128 != 0 && Cout != 64) return DREG_EINVAL;
     if (workspace_bytes < dreg_conv3d_wgrad_workspace_bytes(B, Do, Ho, Wo, Cin, Cout, ksz, 0)) return DREG_EINVAL;
-    const uint32_t nrows = g.M;
-    const int nsplit = dreg_conv3d_wgrad_splits(B, Do, Ho, Wo, Cin, Cout, ksz, 0);
-    uint32_t vps = (uint32_t)((nrows + nsplit - 1) / nsplit);
-    vps = ((vps + 63) / 64) * 64;
-    if (vps == 0) vps = 64;
-    int bm = (Cout % 128 == 0) ? 128 : 64;
-    const uint64_t gbytes = (uint64_t)g.M * Cout * 2, ibytes = (uint64_t)B * Di * Hi * Wi * Cin * 2;
-    if (gbytes >= 0x7fffff00ull || ibytes >= 0x7fffff00ull) return DREG_EINVAL;
-    int bnc = (g.Kpad % 128 == 0 || g.Kpad > 128) ? 128 : 64;
-    if (g_narrow_small >= 2 && (Cout / bm) * ((g.Kpad + bnc - 1) / bnc) * nsplit < g_narrow_thr) {      // the rules of wgrad_impl
-        if (bnc == 128) bnc = 64;
-        if (bm == 128 && (Cout / bm) * (g.Kpad / bnc) * nsplit < g_narrow_thr) bm = 64;
-    }
-    if (g_wgrad_big && Cout % 256 == 0 && (g.Kpad % 256 == 0 || g.Kpad >= 1024) && nrows >= 65536) return DREG_EINVAL;   // (takes the 8-wave tile)
-    const int tilesRow = Cout / bm, tilesCol = (g.Kpad + bnc - 1) / bnc;
+    const WgradChoice c = wgrad_choose(g, 0, true, false, 0, false);
+    if (c.family != WG_GLDS4) return DREG_EINVAL;
     WgradGroupDesc d{};
     d.gout = (const bf16_t*)gout; d.in = (const bf16_t*)in; d.part = (float*)workspace; d.g = g;
-    d.tilesCol = tilesCol; d.tiles = tilesRow * tilesCol; d.nsplit = nsplit; d.vps = vps; d.gbytes = (uint32_t)gbytes; d.ibytes = (uint32_t)ibytes;
-    d.nrows = nrows; d.block0 = 0;
+    d.tilesCol = c.tilesCol; d.tiles = c.tilesRow * c.tilesCol; d.nsplit = c.nsplit; d.vps = c.vps; d.gbytes = (uint32_t)c.gbytes; d.ibytes = (uint32_t)c.ibytes;
+    d.nrows = g.M; d.block0 = 0;
     std::memcpy(desc_host, &d, sizeof(d));
-    *variant = bm * 1000 + bnc;
-    *nblocks = tilesRow * tilesCol * nsplit;
+    *variant = c.bm * 1000 + c.bnc;
+    *nblocks = (int)c.grid.x;
     return DREG_OK;
 }
 // descs_dev: n descriptors of ONE variant in device memory with ascending block0; total_blocks = the sum of their workgroup counts
@@ -2910,33 +2877,17 @@ int dreg_wgrad_reduce_batched(const void* descs_dev, int n, int block_base, int 
     DREG_LAUNCH_CHECK();
     return DREG_OK;
 }
-// Which bf16 weight-gradient kernel a launch of this shape runs (the same rules as wgrad_impl; for the profiler's labels):
-// returns BM * 1000 + BNC (256256 = the 8-wave 256 x 256 tile).  rows: row-list launch; occ: launch with output-row occupancy flags.
+// Which bf16 weight-gradient kernel a launch of this shape runs (wgrad_choose, the choice wgrad_impl launches from; for the profiler's labels):
+// BM * 1000 + BNC of conv_wgrad_glds_kernel (256256 = the 8-wave 256 x 256 tile, 256128 = 4 waves / 32-voxel stages), 1000000 + BM * 1000 + BNC
+// when the launch runs the register-staged conv_wgrad_kernel (an operand of 2 GiB or more), negative when it is refused.  The volume is taken as
+// stride 1 and same-size (Di,Hi,Wi = Do,Ho,Wo).  rows: row-list launch of nrows rows; occ: launch with output-row occupancy flags.
 int dreg_conv3d_wgrad_variant(int B, int Do, int Ho, int Wo, int Cin, int Cout, int ksz, int rows, int nrows, int occ)
 {
-    const int Kpad = dreg_conv3d_kpad(ksz, Cin, 0);
-    const int smax = dreg_conv3d_wgrad_splits(B, Do, Ho, Wo, Cin, Cout, ksz, 0);
-    const int nsplit = rows ? wgrad_row_splits(Cout, Kpad, ksz, (uint32_t)nrows, smax, g_rows_fast && g_wgrad_big == 3 && g_wgrad_ring == 3 && ksz <= 3 && Cout % 256 == 0 &&
-                                               (Kpad % 256 == 0 || Kpad >= 1024) && nrows >= 16384 && Do < 1024 && Ho < 1024 && Wo < 1024) : smax;
-    const long M = (long)B * Do * Ho * Wo;
-    if (!rows && !occ && g_wgrad_big && Cout % 256 == 0 && (Kpad % 256 == 0 || (Kpad >= 1024 && g_wgrad_big == 3 && g_wgrad_ring >= 3 && !g_wgrad_pipe)) && (rows ? nrows : M) >= 65536) return g_wgrad_big == 1 ? 256128 : 256256;
-    if (rows && g_rows_fast && g_wgrad_big == 3 && g_wgrad_ring == 3 && ksz <= 3 && Cout % 256 == 0 && (Kpad % 256 == 0 || Kpad >= 1024) && nrows >= 16384) {   // anti-phase row-list form
-        uint32_t vps = (uint32_t)((nrows + nsplit - 1) / nsplit);
-        vps = ((vps + 63) / 64) * 64;
-        if ((size_t)4 * 32 * 512 * 2 + ((size_t)vps + 5 * 32) * 8 <= (size_t)160 * 1024) return 256256;
-    }
-    if (rows && g_rows_fast && g_wgrad_big == 3 && ksz == 3 && Cout % 256 == 0 && Kpad % 256 == 0 && nrows >= 65536) {   // stride 1, same-size volume assumed
-        uint32_t vps = (uint32_t)((nrows + nsplit - 1) / nsplit);
-        vps = ((vps + 63) / 64) * 64;
-        if ((size_t)2 * 64 * 512 * 2 + (size_t)vps * 8 <= (size_t)160 * 1024) return 256256;
-    }
-    int bm = (Cout % 128 == 0) ? 128 : 64;
-    int bnc = (Kpad % 128 == 0 || Kpad > 128) ? 128 : 64;
-    if (g_narrow_small >= 2 && (Cout / bm) * ((Kpad + bnc - 1) / bnc) * nsplit < g_narrow_thr) {
-        if (bnc == 128) bnc = 64;
-        if (bm == 128 && (Cout / bm) * (Kpad / bnc) * nsplit < g_narrow_thr) bm = 64;
-    }
-    return bm * 1000 + bnc;
+    ConvGeom g;
+    if (fill_geom(g, B, Do, Ho, Wo, Cin, Do, Ho, Wo, Cout, ksz, 1, ksz / 2, 0, 2) || (Cout % 128 != 0 && Cout != 64) || (rows && nrows < 0)) return -1;
+    const WgradChoice c = wgrad_choose(g, 0, true, rows != 0, (uint32_t)nrows, occ != 0);
+    if (c.family == WG_UNSUPPORTED) return -1;
+    return (c.family == WG_REG ? 1000000 : 0) + c.bm * 1000 + c.bnc;
 }
 int dreg_conv3d_wgrad_rows(const void* gout, const void* in, float* dw, void* workspace, size_t workspace_bytes,
                            const int* rows, int nrows,

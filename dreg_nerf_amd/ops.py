@@ -406,8 +406,7 @@ def conv_wgrad(gout, x, w_shape, cin_pad, ksz, stride, pad, use_tr=True, accumul
         tn = "bf16" if dt == L.DT_BF16 else "f32"
         label = f"wgrad B{B} {Di}x{Hi}x{Wi}x{cin_pad} g{Do}x{Ho}x{Wo}x{cout} k{ksz}s{stride}"
         if dt == L.DT_BF16 and use_tr:
-            var = lib.dreg_conv3d_wgrad_variant(B, Do, Ho, Wo, cin_pad, cout, ksz, 0, 0, 0)
-            wname = "conv_wgrad_glds_kernel<256,256,false,8>+reduce" if var == 256256 else f"conv_wgrad_glds_kernel<{var // 1000},{var % 1000},false,4>+reduce"   # 256128 -> <256,128,...>
+            wname = wgrad_kernel_name(lib, B, Do, Ho, Wo, cin_pad, cout, ksz) + "+reduce"
         else:
             wname = f"conv_wgrad_kernel<{tn}>+reduce"
         ev = PROFILER.record(wname, label, 2.0 * B * Do * Ho * Wo * cout * (ksz ** 3) * cin_real)
@@ -619,6 +618,17 @@ def igemm_kernel_name(lib, B, Di, Hi, Wi, cin, Do, Ho, Wo, cout, ksz, stride, pa
     if kind == 1:
         return f"conv_igemm_kernel<{'bf16' if dt == L.DT_BF16 else 'f32'},{to},{bn}>"
     return f"conv_igemm_glds_kernel<{to},{bm},{bn},0,{ap}>" + ("+splitk_reduce" if sk else "")
+
+
+def wgrad_kernel_name(lib, B, Do, Ho, Wo, cin, cout, ksz, is_rows=False, nrows=0, occ=False):
+    """The same for a bf16 weight-gradient launch (dreg_conv3d_wgrad_variant: stride 1, same-size volume): the template arguments rocprofv3 prints."""
+    v = lib.dreg_conv3d_wgrad_variant(B, Do, Ho, Wo, cin, cout, ksz, int(bool(is_rows)), int(nrows), int(bool(occ)))
+    if v < 0:
+        return "conv_wgrad(unsupported)"
+    if v >= 1000000:     # an operand of 2 GiB or more: the register-staged kernel
+        return "conv_wgrad_kernel<bf16>"
+    bm, bnc = v // 1000, v % 1000
+    return f"conv_wgrad_glds_kernel<{bm},{bnc},{'true' if is_rows else 'false'},{8 if bnc == 256 else 4}>"
 
 
 # --------------------------------------------------------------------------- active-set convolution (row lists)

@@ -132,8 +132,7 @@ class PointSetExecutor:
             kind, rows, cin, cout, flags = (info[5 * i + k] for k in range(5))
             fl = 2.0 * rows * cin * cout
             if kind == 2:
-                var = self.lib.dreg_conv3d_wgrad_variant(rows, 1, 1, 1, cin, cout, 1, 0, 0, 0)
-                name = "conv_wgrad_glds_kernel<256,256,false,8>" if var == 256256 else f"conv_wgrad_glds_kernel<{var // 1000},{var % 1000},false,4>"
+                name = ops.wgrad_kernel_name(self.lib, rows, 1, 1, 1, cin, cout, 1)
                 label = f"wgrad B{rows} 1x1x1x{cin} g1x1x1x{cout} k1s1"
             elif kind == 1:     # data gradient: the transposed problem (cout -> cin)
                 name = ops.igemm_kernel_name(self.lib, rows, 1, 1, 1, cout, 1, 1, 1, cin, 1, 1, 0, 1, 0, bool(flags & 4), bool(flags & 1), L.DT_BF16, False)

@@ -225,12 +225,7 @@ class TrunkExecutor:
             out[(i, 0)] = (fname, f"fwd{rows} B{B} {x[1]}x{x[2]}x{x[3]}x{x[4]}->{y[1]}x{y[2]}x{y[3]}x{cout} k{k}s{s}", fl, lo, per_row, f"conv3_brick_kernel<{cout},bf16>", None)
             out[(i, 1)] = (dname, f"dgrad{rows} B{B} {y[1]}x{y[2]}x{y[3]}x{cout}->{x[1]}x{x[2]}x{x[3]}x{cin} k{k}s{s}", fl, li, per_row, f"conv3_brick_kernel<{cin},bf16>", dname_add)
             def wgrad_name(nr, B=B, x=x, y=y, cout=cout, k=k, is_rows=is_rows, first=int(o[1] == 0)):
-                var = lib.dreg_conv3d_wgrad_variant(B, y[1], y[2], y[3], x[4], cout, k, int(is_rows), nr, first)
-                if var == 256256:
-                    return f"conv_wgrad_glds_kernel<256,256,{'true' if is_rows else 'false'},8>"
-                if var == 256128:
-                    return "conv_wgrad_glds_kernel<256,128,false,4>"
-                return f"conv_wgrad_glds_kernel<{var // 1000},{var % 1000},{'true' if is_rows else 'false'},4>"     # the template arguments rocprofv3 prints
+                return ops.wgrad_kernel_name(lib, B, y[1], y[2], y[3], x[4], cout, k, is_rows, nr, first)
             wname = wgrad_name if is_rows else wgrad_name(0)
             out[(i, 2)] = (wname, f"wgrad{rows} B{B} {x[1]}x{x[2]}x{x[3]}x{x[4]} g{y[1]}x{y[2]}x{y[3]}x{cout} k{k}s{s}", fl, lo, per_row, None, None)
         out[(-1, 3)] = ("wgrad_reduce_batched_kernel", "split sums of a backward range -> torch-layout gradients", 0.0, -1, 0.0, None, None)

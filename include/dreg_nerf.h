@@ -132,7 +132,9 @@ int dreg_conv3d_dgrad_s2_acc(const void* gout, const void* wt_class_packed, void
 
 /* Weight gradient (split over voxels, deterministic two-stage reduction):
  * dw[Cout][Cin_real][ksz^3] (fp32, torch layout) (+)= sum_m gout[m,:]^T x in[gather(m, tap), :]. */
-/* which bf16 weight-gradient kernel a launch of this shape runs: BM * 1000 + BNC (256256 = the 8-wave tile, 256128 = 4 waves / 32-voxel stages); for profiler labels */
+/* which bf16 weight-gradient kernel a launch of this shape runs (stride 1, same-size volume; rows / nrows: a row-list launch; occ: with occupancy flags):
+ * BM * 1000 + BNC of conv_wgrad_glds_kernel (256256 = the 8-wave tile, 256128 = 4 waves / 32-voxel stages), 1000000 + BM * 1000 + BNC when an operand of
+ * 2 GiB or more sends the launch to the register-staged conv_wgrad_kernel, negative when the launch is refused; for profiler labels */
 /* which kernel a convolution launch of this shape runs: kind * 1e8 + BM * 1e5 + BN * 100 + AP * 10 + splitK (kind 0 conv_igemm_glds_kernel, 1 conv_igemm_kernel; < 0 unsupported); nrows 0 = dense */
 int dreg_conv3d_igemm_variant(int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int ksz, int stride, int pad,
                               int transposed, int nrows, int has_ws, int has_addend, int dtype);

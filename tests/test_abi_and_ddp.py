@@ -323,6 +323,82 @@ def test_profiler_labels_come_from_the_librarys_dispatch_rules():
     assert lib.dreg_conv3d_wgrad_variant(8, 64, 64, 64, 256, 256, 3, 0, 0, 0) == 256256
     assert lib.dreg_conv3d_wgrad_variant(8, 64, 64, 64, 64, 256, 3, 0, 0, 0) == 256256      # 27 x 64 columns: ragged last tile of the 256-wide form
     assert lib.dreg_conv3d_wgrad_variant(8, 16, 16, 16, 128, 128, 3, 0, 0, 0) == 128128
+    wname = lambda *a: ops.wgrad_kernel_name(lib, *a)
+    assert wname(8, 64, 64, 64, 256, 256, 3) == "conv_wgrad_glds_kernel<256,256,false,8>"
+    assert wname(8, 64, 64, 64, 256, 256, 3, True, 90000) == "conv_wgrad_glds_kernel<256,256,true,8>"
+    assert wname(8, 16, 16, 16, 128, 128, 3) == "conv_wgrad_glds_kernel<128,128,false,4>"
+    assert wname(8, 64, 64, 64, 64, 512, 1) == "conv_wgrad_kernel<bf16>"                    # gout is 2 GiB: the register-staged kernel
+
+
+def test_conv_dispatch_answers_what_was_recorded_before_the_rules_were_stated_once():
+    """tests/golden/conv_dispatch.json holds what the host-only dispatch entry points answered over a shape sweep (tools/make_conv_dispatch_golden.py)
+    when launch, grouped-launch descriptor and profiler label each derived the rules on their own.  The single statement (igemm_choose / wgrad_choose in
+    csrc/conv.hip) must reproduce every recorded value, except where the recorded LABEL disagreed with the recorded build's own launch — there the label
+    is now what wgrad_impl launches:
+      (a) an operand of 2 GiB or more (0x7fffff00 bytes: the buffer descriptors' reach): the register-staged conv_wgrad_kernel, code 1000000 + tile;
+          the old label named a direct-to-LDS tile, the launch's glds_path was false;
+      (b) occupancy flags on a volume with Wo % 64 != 0: the launch drops the flags before it picks the tile, so it runs what the launch without flags runs;
+      (c) row lists with 5^3 taps, >= 65,536 rows, Cout % 256 == 0 and Kpad % 256 == 0: the lockstep 8-wave tile (the launch's test has no ksz clause);
+      (d) row lists whose split holds more than 20,480 rows: the launch refuses (the caller falls back to dense), the label is -1.
+    And on every dense shape the grouped-launch descriptor is offered exactly when the label names a four-wave direct-to-LDS tile, with the same tile."""
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("make_conv_dispatch_golden", os.path.join(root, "tools", "make_conv_dispatch_golden.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    with open(os.path.join(root, "tests", "golden", "conv_dispatch.json")) as f:
+        doc = json.load(f)
+    assert doc["params"] == G.PARAMS, "the sweep of tools/make_conv_dispatch_golden.py is not the recorded one"
+    lib = G.load()
+    want, got = G.unpack(doc), G.collect(lib)
+    for key in ("dense_group", "dense_igemm", "linear_group", "other"):
+        assert got[key] == want[key], key
+    LIMIT = 0x7fffff00
+    four_wave = (128128, 128064, 64128, 64064)
+    shapes = G.dense_shapes()
+    assert len(shapes) >= 720 and len(got["dense_wgrad"]) == 6 * len(shapes)
+    n_big = n_occ = n_fill = 0
+    for i, (B, D, cin, cout, k) in enumerate(shapes):
+        w, g = want["dense_wgrad"][6 * i:6 * i + 6], got["dense_wgrad"][6 * i:6 * i + 6]
+        grp = got["dense_group"][8 * i:8 * i + 8]
+        assert g[2:] == w[2:], (B, D, cin, cout, k)                        # split counts and workspace sizes
+        if max(B * D ** 3 * cout * 2, B * D ** 3 * cin * 2) >= LIMIT:      # (a)
+            assert g[0] // 1000000 == 1 and g[1] == g[0] and w[0] < 1000000, (B, D, cin, cout, k)
+            n_big += 1
+        else:
+            assert g[0] == w[0], (B, D, cin, cout, k)
+            if D % 64 != 0:                                                # (b)
+                assert g[1] == g[0], (B, D, cin, cout, k)
+                n_occ += g[1] != w[1]
+            else:
+                assert g[1] == w[1], (B, D, cin, cout, k)
+        assert (grp[0] == 0) == (g[0] in four_wave), (B, D, cin, cout, k)
+        if grp[0] == 0:
+            assert grp[1] == g[0], (B, D, cin, cout, k)
+            n_fill += 1
+    assert n_big >= 8 and n_occ >= 1 and n_fill >= 100                     # each class is in the sweep
+    n_k5 = n_refused = 0
+    for i, (B, D, cin, cout, k, n) in enumerate(G.row_cases()):
+        w, g = want["rows"][3 * i:3 * i + 3], got["rows"][3 * i:3 * i + 3]
+        assert g[1:] == w[1:], (B, D, cin, cout, k, n)
+        kpad = (k ** 3 * cin + 63) // 64 * 64
+        if max(B * D ** 3 * cout * 2, B * D ** 3 * cin * 2) >= LIMIT:      # (a)
+            assert g[0] // 1000000 == 1 and w[0] < 1000000, (B, D, cin, cout, k, n)
+        elif k == 5:        # outside the anti-phase form (ksz <= 3): at least 1,024 rows per split, at most the dense split count
+            nsplit = min(-(-n // 1024), lib.dreg_conv3d_wgrad_splits(B, D, D, D, cin, cout, k, 0))
+            vps = -(-(-(-n // nsplit)) // 64) * 64
+            if vps > 20480:                                                # (d)
+                assert g[0] == -1, (B, D, cin, cout, k, n)
+                n_refused += 1
+            elif cout % 256 == 0 and kpad % 256 == 0 and n >= 65536 and 2 * 64 * 512 * 2 + vps * 8 <= 160 * 1024:     # (c)
+                assert g[0] == 256256 and w[0] in four_wave, (B, D, cin, cout, k, n)
+                n_k5 += 1
+            else:
+                assert g[0] == w[0], (B, D, cin, cout, k, n)
+        else:
+            assert g[0] == w[0], (B, D, cin, cout, k, n)
+    assert n_k5 >= 1 and n_refused >= 1
 
 
 class _FakeSplit:
