@@ -1918,6 +1918,10 @@ static inline int nblocks(size_t total, int per = 256, int cap = 8192) {
     return (int)(b > (size_t)cap ? cap : (b ? b : 1));
 }
 // rows of one statistics chunk: enough chunks that B grids x chunks fill the chip even for the 8^3 / 4^3 levels of the ResNet
+// bn_partial_kernel and the colsum_*partial kernels place slab z's thread t on granule z * 256 + t % 256 without testing it against CG (the
+// apply kernels do test): a last slab that is not full would read and write past the row.  No layer has such a channel count (more than 256
+// granules, not a multiple of 256: fp32 C = 1536); the entry points that launch those kernels refuse it.
+static inline bool slabs_ragged(int CG) { return CG > 256 && CG % 256 != 0; }
 static inline int bn_rows_per_chunk(int V) { return V >= 262144 ? 512 : V >= 32768 ? 256 : V >= 4096 ? 128 : V >= 512 ? 32 : (V >= 8 ? 8 : V); }
 
 extern "C" {
@@ -2036,13 +2040,13 @@ static int bn3d_fwd_impl(const void* x, const void* res, void* y, const float* g
         return DREG_OK;
     }
     if (train && V < 2) return DREG_EINVAL;      // torch raises for one value per channel
+    if (B > BN_MAX_GRIDS || (train && !presummed && slabs_ragged(CG))) return DREG_EINVAL;      // refused before anything is launched
     if (train && !presummed && !(g_bn_debug_skip & 1)) {
         dim3 grid(nch, B, slabs);
         if (dtype == 0) hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 0>), grid, dim3(256), 0, st, (const bf16_t*)x, nullptr, nullptr, nullptr, workspace, V, C, rpc, 0);
         else hipLaunchKernelGGL((bn_partial_kernel<float, 0>), grid, dim3(256), 0, st, (const float*)x, nullptr, nullptr, nullptr, workspace, V, C, rpc, 0);
         DREG_LAUNCH_CHECK();
     }
-    if (B > BN_MAX_GRIDS) return DREG_EINVAL;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64 * (B < 8 ? B : 8)), 0, st, workspace, gamma, beta, running_mean, running_var,
                        scale_shift, mean_rstd, B, presummed ? V / sums_rows_per_chunk : nch, C, V, eps, momentum, train);
     DREG_LAUNCH_CHECK();
@@ -2109,6 +2113,7 @@ static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const flo
         DREG_LAUNCH_CHECK();
         return DREG_OK;
     }
+    if (B > BN_MAX_GRIDS || slabs_ragged(CG)) return DREG_EINVAL;      // refused before anything is launched
     dim3 grid(nch, B, slabs);
     // residual + ReLU layers (the last BatchNorm of a bottleneck): the masked gradient the statistics pass forms IS the residual branch's
     // gradient — it is stored there, and the apply pass reads it back instead of dy and y (one activation-sized read less, same values)
@@ -2117,7 +2122,6 @@ static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const flo
     else if (dtype == 0) hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)y, mean_rstd, workspace, V, C, rpc, relu, scale_shift, g_stored ? (bf16_t*)dres : nullptr);
     else hipLaunchKernelGGL((bn_partial_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, (const float*)y, mean_rstd, workspace, V, C, rpc, relu, scale_shift, g_stored ? (float*)dres : nullptr);
     DREG_LAUNCH_CHECK();
-    if (B > BN_MAX_GRIDS) return DREG_EINVAL;
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64 * (B < 8 ? B : 8)), 0, st, workspace, coef, dgamma, dbeta, B, nch, C, V, accumulate);
     DREG_LAUNCH_CHECK();
     const size_t tg = (size_t)B * V * CG;
@@ -2139,6 +2143,7 @@ int dreg_bn_relu_maxpool_fwd(const void* x, void* pooled, uint8_t* argmax, const
     if (C % 8 || B > BN_MAX_GRIDS || (train && V < 2)) return DREG_EINVAL;
     const int rpc = bn_rows_per_chunk(V), nch = (V + rpc - 1) / rpc;
     const int CG = C / 8, slabs = (CG + 255) / 256;
+    if (train && slabs_ragged(CG)) return DREG_EINVAL;
     if (train) {
         hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 0>), dim3(nch, B, slabs), dim3(256), 0, st, (const bf16_t*)x, nullptr, nullptr, nullptr, workspace, V, C, rpc, 0);
         DREG_LAUNCH_CHECK();
@@ -2298,6 +2303,7 @@ int dreg_colsum(const void* g, float* out, float* workspace, size_t M, int C, in
     const int rpc = colsum_rows_per_chunk(M);
     const int nch = (int)((M + rpc - 1) / rpc);
     const int CG = C / G, slabs = (CG + 255) / 256;
+    if (slabs_ragged(CG)) return DREG_EINVAL;
     if (dtype == 0) hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(nch, slabs), dim3(256), 0, st, (const bf16_t*)g, workspace, M, C, rpc);
     else hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(nch, slabs), dim3(256), 0, st, (const float*)g, workspace, M, C, rpc);
     DREG_LAUNCH_CHECK();
@@ -2330,6 +2336,7 @@ int dreg_colsum_rows(const void* g, const int* rows, int nrows, float* out, floa
     const int rpc = colsum_rows_per_chunk((size_t)nrows);
     const int nch = (nrows + rpc - 1) / rpc;
     const int CG = C / G, slabs = (CG + 255) / 256;
+    if (slabs_ragged(CG)) return DREG_EINVAL;
     if (dtype == 0) hipLaunchKernelGGL(colsum_rows_partial_kernel<bf16_t>, dim3(nch, slabs), dim3(256), 0, st, (const bf16_t*)g, rows, workspace, nrows, C, rpc);
     else hipLaunchKernelGGL(colsum_rows_partial_kernel<float>, dim3(nch, slabs), dim3(256), 0, st, (const float*)g, rows, workspace, nrows, C, rpc);
     DREG_LAUNCH_CHECK();

@@ -193,7 +193,10 @@ int dreg_wgrad_group_launch(const void* descs_dev, int n, int variant, int total
 /* ---------------------------------------------------------------------------------------------- FPN3D companions
  * BatchNorm3d with the reference's one-grid-per-call statistics (resnet3d.py:121,159; nerf_regtr.py:135), fused
  * residual add + ReLU (resnet3d.py:95-113). x,res,y: [B,V,C]; scale_shift, mean_rstd: fp32 [B,C,2] (saved for bwd);
- * workspace fp32 [B * dreg_bn_num_chunks(V) * C * 2].  train = 0 uses the running statistics. */
+ * workspace fp32 [B * dreg_bn_num_chunks(V) * C * 2].  train = 0 uses the running statistics.
+ * DREG_EINVAL, before anything is launched: C not a multiple of the 16-byte granule (8 bf16 / 4 fp32 channels); B > 256 or training with V < 2
+ * outside the one-launch small form (dreg_bn_small); and — BatchNorm statistics passes, the fused stem forward, dreg_colsum, dreg_colsum_rows —
+ * more than 256 granules that are not a multiple of 256 (fp32 C = 1536: the last slab of 256 granules would not be full). */
 int dreg_bn_num_chunks(int V);
 int dreg_bn3d_fwd(const void* x, const void* res, void* y, const float* gamma, const float* beta,
                   float* running_mean, float* running_var, float* scale_shift, float* mean_rstd, float* workspace,
