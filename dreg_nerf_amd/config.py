@@ -47,6 +47,9 @@ def config_parser(argv=None):
                    help="eval: per scene, transformation_est.json and the registration's point clouds as PLY files (eval_nerf_regtr.py:313-438)")
     p.add_argument("--render_views", action="store_true",
                    help="eval: per scene, render both NeRF blocks under the ground-truth, predicted and no alignment (render_videos, eval_nerf_regtr.py:113-172,345-369)")
+    p.add_argument("--render_merged", action="store_true",
+                   help="eval: per scene, render both NeRF blocks as ONE scene (fused two-block renderer) under the ground-truth and the predicted pose, and write "
+                        "PSNR / SSIM between the two to merged_metrics.json (the photometric cost of the pose error; needs the block checkpoints)")
     p.add_argument("--eval_images", action="store_true",
                    help="eval_ngp_nerf.py: render the held-out views of --scene and write PSNR / SSIM per view to eval/<scene>/[block_k/]metrics.json (evaluate, eval_ngp_nerf.py:159-244 of the reference)")
     p.add_argument("--point_cloud", action="store_true",

@@ -241,6 +241,8 @@ SIGNATURES = {
     "dreg_surface_visibility_multi_waves": (I, [P, I, ctypes.c_long, I, P]),
     # render.hip
     "dreg_ngp_render": (I, [P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
+    # render_pair.hip: n_rays, the source block's arguments, the target block's, then power, early_stop_eps, bkgd, the outputs, queue, stream
+    "dreg_ngp_render_pair": (I, [ctypes.c_long] + ([P, P, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 4 + [P]) * 2 + [F, F, P] + [P] * 7),
     # render_train.hip
     "dreg_ngp_render_train": (I, [P, P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
     "dreg_ngp_render_bwd_workspace_bytes": (Z, [ctypes.c_long]),
@@ -287,6 +289,7 @@ PROBE_SIGNATURES = {
     "dreg_visibility_set_waves": (None, [I]),
     "dreg_visibility_set_pass_bound": (I, [ctypes.c_long]),
     "dreg_render_set_waves": (None, [I]),
+    "dreg_render_pair_set_waves": (None, [I]),
     "dreg_render_bwd_set_waves": (None, [I]),
 }
 PROBE_LIB_PATH = os.path.join(_HERE, "libdreg_nerf_hip_probe.so")

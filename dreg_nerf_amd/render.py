@@ -4,7 +4,11 @@ NeRFPoseOnlyDataset (conerf/datasets/register/nerf_pose_only_dataset.py:56-152) 
 (render_videos, eval_nerf_regtr.py:113-172 and :345-369 of the reference).
 
 The marching / compositing rule is stated in csrc/render.hip and DESIGN.md ("Volume renderer"); nerfacc is absent from the reference tree,
-so parity is unpinned and that rule is the specification (CPU restatement: tests/render_restatement.py)."""
+so parity is unpinned and that rule is the specification (CPU restatement: tests/render_restatement.py).
+
+A registered pair of blocks as ONE scene goes through the fused two-block kernel of csrc/render_pair.hip (rays_to_block, render_pair_image,
+render_pair_views, and render_scene_merged for eval_nerf_regtr.py --render_merged; rule: DESIGN.md §3e, CPU restatement:
+tests/render_pair_restatement.py)."""
 import collections
 import ctypes
 import math
@@ -133,6 +137,120 @@ def _render(field, occupancy_grid, rays, scene_aabb, near_plane, far_plane, rend
     return rgb.view(*shp[:-1], 3), opacity.view(*shp[:-1], 1), depth.view(*shp[:-1], 1), n_samples
 
 
+# ---------------------------------------------------------------------------------------------------------------- a registered pair as one scene
+def _pose44(pose: torch.Tensor) -> torch.Tensor:
+    """A [3,4] or [4,4] pose as fp64 [4,4] on the host."""
+    P = pose.detach().double().cpu().reshape(-1, 4)
+    if P.shape[0] == 3:
+        P = torch.cat([P, torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=torch.float64)])
+    if P.shape != (4, 4):
+        raise ValueError(f"pose must be [3,4] or [4,4], got {tuple(pose.shape)}")
+    return P
+
+
+def rays_to_block(rays: Rays, pose: torch.Tensor) -> Rays:
+    """Rays given in the frame `pose` = [R|t] maps TO, expressed in the frame it maps FROM (target-frame rays for the source block of a registered
+    pair): o' = R^T (o - t), d' = R^T d / |R^T d|, formed in fp64 and rounded to fp32.  pose: [3,4] or [4,4]; shapes are kept."""
+    P = _pose44(pose).to(rays.origins.device)
+    Rm, t = P[:3, :3], P[:3, 3]
+    o = (rays.origins.double() - t) @ Rm                       # row vectors: (R^T v)^T = v^T R
+    d = rays.viewdirs.double() @ Rm
+    d = d / torch.linalg.norm(d, dim=-1, keepdim=True)
+    return Rays(o.float(), d.float())
+
+
+PAIR_OPTS = ("scene_aabb", "near_plane", "far_plane", "render_step_size", "alpha_thre", "cone_angle")
+
+
+def _pair_block_args(field, grid, rays, opts, center, dev, keep):
+    """One block's arguments of dreg_ngp_render_pair (the C ABI's order); the tensors and ctypes arrays they point into are appended to `keep`."""
+    base16, col16 = field._prepared()
+    o = rays.origins.reshape(-1, 3).to(dev).float().contiguous()
+    d = rays.viewdirs.reshape(-1, 3).to(dev).float().contiguous()
+    roi, b8, bits = _grid_parts(grid, dev)
+    f6 = lambda v: (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
+    near, far = opts.get("near_plane"), opts.get("far_plane")
+    c3 = (ctypes.c_float * 3)(*[float(v) for v in torch.as_tensor(center).reshape(-1).tolist()])
+    arrs = [f6(roi), f6(opts["scene_aabb"]), f6(field._aabb_host()), c3]
+    keep.extend([o, d, b8, bits, base16, col16] + arrs)
+    return [L.ptr(o), L.ptr(d), L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
+            base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+            col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
+            *field._levels, arrs[0], arrs[1], arrs[2],
+            -math.inf if near is None else float(near), math.inf if far is None else float(far),
+            float(opts.get("render_step_size", 1e-3)), float(opts.get("alpha_thre") or 0.0), arrs[3]]
+
+
+def render_pair_image(src_field, src_grid, tgt_field, tgt_grid, rays, pose, src_opts, tgt_opts, src_center, tgt_center, power: float = 4.0,
+                      render_bkgd: Optional[torch.Tensor] = None):
+    """A registered pair of blocks rendered as ONE scene by the fused two-block kernel (csrc/render_pair.hip): rays with origins /
+    viewdirs shaped [N,3] or [H,W,3] in the TARGET frame, pose = [R|t] ([3,4] or [4,4]) mapping the source frame to the target frame ->
+    (colors [...,3], opacities [...,1], depths [...,1], weight_src [...,1], n_rendering_samples: int); weight_src is the part of the opacity that
+    source samples contributed.  *_opts: dicts with scene_aabb, near_plane, far_plane, render_step_size, alpha_thre (of that block's training);
+    *_center: the centroid of the block's cameras in its own frame; power: the exponent of the overlap weight.  Inference only."""
+    for f in (src_field, tgt_field):
+        if f.training:
+            raise RuntimeError("render_pair_image: the fused renderer is inference only (no backward); call it under torch.no_grad() with eval-mode fields")
+    if rays.origins.requires_grad or rays.viewdirs.requires_grad:
+        raise RuntimeError("render_pair_image: the fused renderer is inference only (no backward); call it under torch.no_grad() with eval-mode fields")
+    for f, opts in ((src_field, src_opts), (tgt_field, tgt_opts)):
+        unknown = set(opts) - set(PAIR_OPTS)
+        if unknown:
+            raise TypeError(f"render_pair_image: unknown options {sorted(unknown)} (known: {PAIR_OPTS})")
+        if float(opts.get("cone_angle") or 0.0) != 0.0:
+            raise NotImplementedError("render_pair_image: cone_angle != 0 (unbounded marching) is not supported")
+        if opts.get("scene_aabb") is None or getattr(f, "unbounded", False):
+            raise NotImplementedError("render_pair_image: unbounded scenes (no scene aabb / contracted field) are not supported")
+    with torch.no_grad():
+        lib = L.load()
+        shp = rays.origins.shape
+        dev = tgt_field._prepared()[0].device
+        if src_field._prepared()[0].device != dev:
+            raise ValueError("render_pair_image: both blocks must be on the same device")
+        keep = []
+        src_args = _pair_block_args(src_field, src_grid, rays_to_block(rays, pose), src_opts, src_center, dev, keep)
+        tgt_args = _pair_block_args(tgt_field, tgt_grid, rays, tgt_opts, tgt_center, dev, keep)
+        n = rays.origins.reshape(-1, 3).shape[0]
+        bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(v) for v in torch.as_tensor(render_bkgd).reshape(-1).tolist()]
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        opacity, depth, wsrc = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        counters = torch.zeros(2, dtype=torch.int64, device=dev)          # surviving samples, then the ray queue
+        visibility.OVERRUN.check()
+        L.check(lib.dreg_ngp_render_pair(n, *src_args, *tgt_args, float(power), 1e-4, (ctypes.c_float * 3)(*bk),
+                                         L.ptr(rgb), L.ptr(opacity), L.ptr(depth), L.ptr(wsrc), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
+                "dreg_ngp_render_pair")
+        visibility.OVERRUN.watch(counters[1:])
+        n_samples = int(counters[0].item())
+        visibility.OVERRUN.check(wait=True)
+        return rgb.view(*shp[:-1], 3), opacity.view(*shp[:-1], 1), depth.view(*shp[:-1], 1), wsrc.view(*shp[:-1], 1), n_samples
+
+
+def block_pair_opts(meta) -> dict:
+    """The options render_pair_image takes for one block, from load_render_block's meta (what render_views passes to render_image)."""
+    return dict(scene_aabb=meta["aabb_host"], near_plane=meta.get("near_plane"), far_plane=meta.get("far_plane"),
+                render_step_size=float(meta["render_step_size"]), alpha_thre=float(meta.get("alpha_thre") or 0.0),
+                cone_angle=float(meta.get("cone_angle") or 0.0))
+
+
+def render_pair_views(blocks, pose: torch.Tensor, poses_c2w: torch.Tensor, K: torch.Tensor, W: int, H: int, bkgd=(1.0, 1.0, 1.0)):
+    """render_views for a registered pair: blocks = ((field, grid, meta) of the source, of the target), pose maps the source frame to the target
+    frame, poses_c2w [N,4,4] are cameras in the TARGET frame.  The blocks' camera centroids come from meta["camera_poses"].  Returns lists of
+    device tensors: rgb [H,W,3], depth [H,W,1], weight_src [H,W,1]."""
+    (sf, sg, sm), (tf, tg, tm) = blocks
+    dev = tf._prepared()[0].device
+    bk = torch.tensor(bkgd, dtype=torch.float32)
+    centers = [torch.as_tensor(m["camera_poses"]).float()[:, :3, 3].mean(0).cpu() for m in (sm, tm)]
+    so, to = block_pair_opts(sm), block_pair_opts(tm)
+    rgbs, depths, shares = [], [], []
+    for c2w in poses_c2w:
+        rays = pixel_rays(c2w.to(dev), K, W, H)
+        rgb, _, depth, wsrc, _ = render_pair_image(sf, sg, tf, tg, rays, pose, so, to, centers[0], centers[1], render_bkgd=bk)
+        rgbs.append(rgb)
+        depths.append(depth)
+        shares.append(wsrc)
+    return rgbs, depths, shares
+
+
 def load_render_block(path: str, device):
     """(field, BlockGrid, meta) of a NeRF block checkpoint for rendering, through visibility.load_block's cache (meta has near_plane / far_plane)."""
     field, _, meta = visibility.load_block(path, device)
@@ -232,6 +350,52 @@ def render_scene_views(output_dir: str, src_path: str, tgt_path: str, pose_gt: t
         src_rgbs, src_depths = renderer(src_path, src_poses, K, W, H)
         tgt_rgbs, tgt_depths = renderer(tgt_path, tgt_poses, K, W, H)
         write_render_set(output_dir, prefix, src_rgbs, src_depths, tgt_rgbs, tgt_depths)
+
+
+def _stack_metrics(pred, gt):
+    """Per-view PSNR / SSIM of two image stacks through the fused metrics kernel (one call): lists of floats."""
+    from . import image_metrics as IM
+    m = IM.image_metrics(torch.stack(list(pred)).contiguous(), torch.stack(list(gt)).contiguous())
+    return m["psnr"].cpu().tolist(), m["ssim"].cpu().tolist()
+
+
+def render_scene_merged(output_dir: str, src_path: str, tgt_path: str, pose_gt: torch.Tensor, pose_pred: torch.Tensor, dataset: str, device,
+                        renderer=None, metrics=None):
+    """--render_merged for one scene: both blocks rendered as ONE scene (render_pair_views) from every camera of both blocks, expressed in the
+    target frame, under the ground-truth pose (prefix gt) and the predicted pose (prefix aligned): {prefix}_merged_images/rgb_i.png, depth_i.png
+    and src_share_i.png (the source block's share of the opacity, grey).  merged_metrics.json holds PSNR / SSIM of the aligned views against
+    the gt views — the photometric cost of the pose error; no ground-truth images are needed.
+    renderer(pose, poses_c2w, K, W, H) -> (rgbs, depths, shares) and metrics(aligned_rgbs, gt_rgbs) -> (psnrs, ssims) may be injected (tests)."""
+    import json
+    K, W, H = intrinsics(dataset)
+    if renderer is None:
+        blocks = tuple(load_render_block(p, device) for p in (src_path, tgt_path))
+        cams = [b[2]["camera_poses"] for b in blocks]
+
+        def renderer(pose, poses, K_, W_, H_):
+            return render_pair_views(blocks, pose, poses, K_, W_, H_)
+    else:
+        cams = [block_camera_poses(p) for p in (src_path, tgt_path)]
+    metrics = metrics or _stack_metrics
+    os.makedirs(output_dir, exist_ok=True)
+    sets = pose_sets(cams[0], cams[1], pose_gt, pose_pred)
+    stacks = {}
+    for prefix, P in (("gt", pose_gt), ("aligned", pose_pred)):
+        rgbs, depths, shares = renderer(P, sets[prefix][1], K, W, H)              # (P @ src cameras, tgt cameras): all in the target frame
+        stacks[prefix] = rgbs
+        d = os.path.join(output_dir, prefix + "_merged_images")
+        os.makedirs(d, exist_ok=True)
+        for i in range(len(rgbs)):
+            rgb, depth, share = (np.asarray(v.cpu() if torch.is_tensor(v) else v) for v in (rgbs[i], depths[i], shares[i]))
+            _png(os.path.join(d, f"rgb_{i}.png"), rgb)
+            _png(os.path.join(d, f"depth_{i}.png"), colorize_depth(depth.squeeze(-1)))
+            _png(os.path.join(d, f"src_share_{i}.png"), np.repeat(share.reshape(H, W, 1), 3, axis=2))
+    psnr, ssim = metrics(stacks["aligned"], stacks["gt"])
+    out = {"views": [{"psnr": float(p), "ssim": float(s)} for p, s in zip(psnr, ssim)],
+           "psnr_mean": float(np.mean(psnr)), "ssim_mean": float(np.mean(ssim))}
+    with open(os.path.join(output_dir, "merged_metrics.json"), "w") as f:
+        json.dump(out, f, indent=2)
+    return out
 
 
 def block_camera_poses(path: str) -> torch.Tensor:

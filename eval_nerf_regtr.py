@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Evaluate NeRF registration on MI355X — drop-in for the metric part of the reference's eval_nerf_regtr.py
 (:224-301; with --dump_outputs also its per-scene transformation_est.json and PLY point clouds, :313-438; with --render_views the renders of
-both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369; with --render_merged, which the reference lacks,
+both blocks rendered as one scene under the ground-truth and the predicted pose and merged_metrics.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -72,7 +73,7 @@ def main():
     if CheckPointManager(verbose=rank == 0).load_no_config(ckpt_path, models={"model": model}, map_location=dev) == 0 and not os.path.exists(ckpt_path):
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows = {}, {}
-    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views
+    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
     # whatever the rank count — the gathered metrics file does not depend on the sharding (dreg_nerf_amd/eval_shard.py)
@@ -127,6 +128,14 @@ def main():
                     render_scene_views(scene_dir, sp, tp, data["pose"][0], pred["pose"][-1][0], cfg.dataset, dev)
                 else:
                     print(f"{data['scene']}: no NeRF blocks on disk, views not rendered", flush=True)
+            if cfg.render_merged:  # both blocks as ONE scene under the gt and the predicted pose, and what the pose error costs on screen
+                sp, tp = data.get("src_nerf_path", ""), data.get("tgt_nerf_path", "")
+                if sp and tp and os.path.exists(sp) and os.path.exists(tp):
+                    from dreg_nerf_amd.render import render_scene_merged
+                    mm = render_scene_merged(scene_dir, sp, tp, data["pose"][0], pred["pose"][-1][0], cfg.dataset, dev)
+                    print(f"{data['scene']}: merged render, aligned vs gt PSNR {mm['psnr_mean']:.2f} dB, SSIM {mm['ssim_mean']:.4f}", flush=True)
+                else:
+                    print(f"{data['scene']}: no NeRF blocks on disk, merged scene not rendered", flush=True)
             if cfg.fgr_baseline:   # the reference's baseline on the two voxel point clouds (global_registration.py:96-116)
                 T, sec = fgr.run_registration(_points(data, "src"), _points(data, "tgt"))
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])

@@ -736,6 +736,31 @@ int dreg_ngp_render(const float* origins, const float* viewdirs, long n_rays, co
                     float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
                     float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- a registered pair of blocks as one scene
+ * (csrc/render_pair.hip; rule: DESIGN.md §3e) Every ray is marched through the source block (src_*) and the target block (tgt_*) at once,
+ * each on its own lattice, and their samples are composited in depth order (the source's first on a tie); where both blocks cover a sample its
+ * density is weighted by inverse distance to the blocks' camera centroids (power = the exponent p), so the shared region is not counted twice.
+ * Per block the arguments are dreg_ngp_render's, with origins / viewdirs in THAT block's frame (the caller transforms the rays; the kernel
+ * knows nothing of the pose), plus center: the centroid of the block's cameras in its frame, 3 floats in HOST memory.  Outputs as
+ * dreg_ngp_render plus weight_src fp32 [n_rays], the part of the opacity that came from source samples.  n_samples and queue are zeroed by
+ * the caller on `stream`; bit 63 of the queue word is set if the launch reached its pass bound.  Never allocates; with one block's grid
+ * empty the results equal dreg_ngp_render's of the other block bit for bit. */
+int dreg_ngp_render_pair(long n_rays,
+                         const float* src_origins, const float* src_viewdirs, const uint8_t* src_binary, int src_rx, int src_ry, int src_rz,
+                         const uint32_t* src_coarse_bits, const void* src_table, const void* src_w1, const void* src_w2,
+                         const void* src_cw1, const void* src_cw2, const void* src_cw3,
+                         const uint32_t* src_offset, const uint32_t* src_size, const uint32_t* src_res, const float* src_scale, const uint32_t* src_hashed,
+                         const float* src_roi_aabb, const float* src_scene_aabb, const float* src_model_aabb,
+                         float src_near_plane, float src_far_plane, float src_render_step_size, float src_alpha_thre, const float* src_center,
+                         const float* tgt_origins, const float* tgt_viewdirs, const uint8_t* tgt_binary, int tgt_rx, int tgt_ry, int tgt_rz,
+                         const uint32_t* tgt_coarse_bits, const void* tgt_table, const void* tgt_w1, const void* tgt_w2,
+                         const void* tgt_cw1, const void* tgt_cw2, const void* tgt_cw3,
+                         const uint32_t* tgt_offset, const uint32_t* tgt_size, const uint32_t* tgt_res, const float* tgt_scale, const uint32_t* tgt_hashed,
+                         const float* tgt_roi_aabb, const float* tgt_scene_aabb, const float* tgt_model_aabb,
+                         float tgt_near_plane, float tgt_far_plane, float tgt_render_step_size, float tgt_alpha_thre, const float* tgt_center,
+                         float power, float early_stop_eps, const float* bkgd,
+                         float* rgb, float* opacity, float* depth, float* weight_src, unsigned long long* n_samples, void* queue, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- training of a NeRF block
  * (csrc/render.hip, csrc/render_train.hip; rule: DESIGN.md §3c).
  * dreg_ngp_render_train = dreg_ngp_render with stratified marching: ray i starts at t_min + jitter[i] * render_step_size, jitter fp32 [n_rays]

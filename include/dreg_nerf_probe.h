@@ -48,6 +48,7 @@ void dreg_ngp_set_xcd_levels(int on);                /* 1 (default): dreg_ngp_de
 int dreg_visibility_set_pass_bound(long passes);   /* test hook: passes of the persistent visibility kernels' march loop per wave (0 = default 2^22); a launch that reaches it sets bit 63 of its ray counter words */
 void dreg_visibility_set_waves(int n);               /* one-wave workgroups of dreg_surface_visibility_queue's persistent launch (default 4096 = 256 CUs x 16) */
 void dreg_render_set_waves(int n);                   /* one-wave workgroups of dreg_ngp_render's persistent launch (default 2048 = 256 CUs x 8); same results at every width */
+void dreg_render_pair_set_waves(int n);              /* one-wave workgroups of dreg_ngp_render_pair's persistent launch (default 2048); same results at every width */
 void dreg_render_bwd_set_waves(int n);               /* one-wave workgroups of dreg_ngp_render_bwd's persistent launch (default 2048); same gradients at every width */
 void dreg_conv_set_narrow_small(int on);              /* 1 (default): launches of < 224 128 x 128 tiles use 128 x 64 tiles (twice the workgroups) */
 
