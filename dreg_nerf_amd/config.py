@@ -56,6 +56,15 @@ def config_parser(argv=None):
                    help="eval_ngp_nerf.py: depth-range point cloud of the block's training cameras, point_cloud.ply next to the checkpoint (generate_point_cloud, eval_ngp_nerf.py:246-334 of the reference)")
     p.add_argument("--fgr_baseline", action="store_true",
                    help="also run the Fast Global Registration baseline on every pair and write fgr_metrics_{split}.json (eval_nerf_regtr.py:303-311 of the reference)")
+    p.add_argument("--refine_pose", action="store_true",
+                   help="eval_nerf_regtr.py: refine every predicted pose by point-to-plane ICP on the two voxel point clouds (fused kernels, DESIGN.md 3f; the reference's "
+                        "refine_registration, global_registration.py:85-93) and write refined_metrics_{split}.json next to metrics_{split}.json, which is unchanged")
+    p.add_argument("--icp_max_dist", type=float, default=0.05, help="--refine_pose: correspondence distance threshold")
+    p.add_argument("--icp_iters", type=int, default=30, help="--refine_pose: iteration limit")
+    p.add_argument("--icp_normals", type=str, default="field", choices=["field", "pca"],
+                   help="--refine_pose: target normals from the target block's density gradient (needs the block's checkpoint, else PCA) or by neighbourhood PCA")
+    p.add_argument("--normals", action="store_true",
+                   help="eval_ngp_nerf.py --point_cloud: also write the field's normals (-grad density, normalised) at the points into point_cloud.ply")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

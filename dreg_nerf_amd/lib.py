@@ -251,6 +251,11 @@ SIGNATURES = {
     # image_metrics.hip
     "dreg_image_metrics_workspace_bytes": (Z, [I, I, I, I]),
     "dreg_image_metrics": (I, [P, P, I, I, I, I, P] + [P] * 6 + [P, Z, P]),
+    # ngp_grad.hip
+    "dreg_ngp_density_grad": (I, [P] * 7 + [P] * 5 + [P, I, I, P]),
+    # icp.hip
+    "dreg_icp_workspace_bytes": (Z, [I, I]),
+    "dreg_icp_refine": (I, [P, I, P, P, P, P, I, P, F, I, I, I, P, F, I] + [ctypes.c_double] * 3 + [P, P, P, P, P, Z, P]),
 }
 
 

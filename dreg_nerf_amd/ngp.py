@@ -188,6 +188,28 @@ class NGPradianceField(nn.Module):
             return density, raw[:, 1:].float().view(*shp, self.geo_feat_dim)
         return density
 
+    @torch.no_grad()
+    def query_density_grad(self, x: torch.Tensor, return_mask: bool = False):
+        """x [...,3] world -> (density [...,1], grad [...,3] = d density / d x): csrc/ngp_grad.hip, DESIGN.md §3f.  The density is query_density's bit
+        for bit; the gradient is that of the trilinear hash-grid field (it jumps across cell faces) and exactly zero outside the aabb.  With
+        return_mask also the uint64 ReLU mask of the density net's hidden layer per point (as int64 bits).  Bounded fields only."""
+        if self.unbounded:
+            raise NotImplementedError("query_density_grad: the gradient of the contracted (unbounded) field is not implemented")
+        lib = L.load()
+        import ctypes
+        base16, _ = self._prepared()
+        shp = x.shape[:-1]
+        x = x.reshape(-1, 3).contiguous().float()
+        n = x.shape[0]
+        density = torch.empty(n, dtype=torch.float32, device=x.device)
+        grad = torch.empty(n, 3, dtype=torch.float32, device=x.device)
+        mask = torch.empty(n, dtype=torch.int64, device=x.device) if return_mask else None
+        aabb = (ctypes.c_float * 6)(*self._aabb_host())
+        L.check(lib.dreg_ngp_density_grad(L.ptr(x), base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+                                          L.ptr(density), L.ptr(grad), L.ptr(mask), *self._levels, aabb, n, 0, L.stream()), "dreg_ngp_density_grad")
+        out = (density.view(*shp, 1), grad.view(*shp, 3))
+        return out + (mask.view(*shp),) if return_mask else out
+
     def dir_bias(self, dirs: torch.Tensor) -> torch.Tensor:
         """c_k = fp16(W1[:, :16]) . fp16(SH4(dir_k))  for the colour net's first layer: [ndir, 64] fp32."""
         _, col16 = self._prepared()
@@ -236,6 +258,15 @@ class NGPradianceField(nn.Module):
         assert directions is not None and positions.shape == directions.shape, f"{positions.shape} v.s. {None if directions is None else directions.shape}"
         density, feat = self.query_density(positions, return_feat=True)
         return self.query_rgb(directions, feat), density
+
+
+def field_normals(field: NGPradianceField, x: torch.Tensor) -> torch.Tensor:
+    """Surface normals of a block at the points x [N,3]: -grad(density) / |grad(density)| (density grows into the surface), exact zeros where
+    the gradient vanishes (outside the aabb, or a flat cell).  No neighbourhood search: the field differentiates itself."""
+    _, g = field.query_density_grad(x.reshape(-1, 3))
+    norm = g.norm(dim=1, keepdim=True)
+    ok = (norm > 0) & torch.isfinite(norm)
+    return torch.where(ok, -g / torch.where(ok, norm, torch.ones_like(norm)), torch.zeros_like(g))
 
 
 def sh4(d: torch.Tensor) -> torch.Tensor:

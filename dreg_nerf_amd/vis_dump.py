@@ -11,18 +11,30 @@ import numpy as np
 import torch
 
 
-def write_ply(path: str, xyz, rgb=None) -> None:
-    """xyz [N,3] float; rgb [N,3] in [0,1] (open3d's colour convention) or None."""
+def write_ply(path: str, xyz, rgb=None, normals=None) -> None:
+    """xyz [N,3] float; rgb [N,3] in [0,1] (open3d's colour convention) or None; normals [N,3] or None (double nx / ny / nz after the position,
+    where open3d's writer puts them).  Without normals the file is what it was before the argument existed, byte for byte."""
     xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
     n = xyz.shape[0]
     props = "property double x\nproperty double y\nproperty double z\n"
+    fields = [("p", "<f8", 3)]
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        assert normals.shape[0] == n
+        props += "property double nx\nproperty double ny\nproperty double nz\n"
+        fields.append(("n", "<f8", 3))
     if rgb is not None:
         rgb = np.asarray(rgb, dtype=np.float64).reshape(-1, 3)
         assert rgb.shape[0] == n
         props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-        rec = np.empty(n, dtype=[("p", "<f8", 3), ("c", "u1", 3)])
+        fields.append(("c", "u1", 3))
+    if len(fields) > 1:
+        rec = np.empty(n, dtype=fields)
         rec["p"] = xyz
-        rec["c"] = np.clip(np.round(rgb * 255.0), 0, 255).astype(np.uint8)
+        if normals is not None:
+            rec["n"] = normals
+        if rgb is not None:
+            rec["c"] = np.clip(np.round(rgb * 255.0), 0, 255).astype(np.uint8)
         body = rec.tobytes()
     else:
         body = xyz.astype("<f8").tobytes()
@@ -30,6 +42,20 @@ def write_ply(path: str, xyz, rgb=None) -> None:
         f.write((f"ply\nformat binary_little_endian 1.0\ncomment Created by dreg_nerf_amd (open3d point-cloud layout)\n"
                  f"element vertex {n}\n{props}end_header\n").encode("ascii"))
         f.write(body)
+
+
+def read_ply_normals(path: str):
+    """Reader for a file written with normals (tests): returns (xyz float64 [N,3], normals float64 [N,3], rgb uint8 [N,3] or None)."""
+    with open(path, "rb") as f:
+        header = b""
+        while not header.endswith(b"end_header\n"):
+            header += f.readline()
+        lines = header.decode("ascii").splitlines()
+        n = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
+        assert any(l == "property double nx" for l in lines), "no normals in this file"
+        colored = any(l.startswith("property uchar") for l in lines)
+        rec = np.frombuffer(f.read(), dtype=[("p", "<f8", 3), ("n", "<f8", 3)] + ([("c", "u1", 3)] if colored else []), count=n)
+        return rec["p"].copy(), rec["n"].copy(), (rec["c"].copy() if colored else None)
 
 
 def read_ply(path: str):

@@ -36,6 +36,33 @@ def _row(err, dt):
     return {"R_mean": float(err["R_error_mean"]), "t_mean": float(err["t_error_mean"]), "R_med": float(err["R_error_med"]), "t_med": float(err["t_error_med"]), "time": dt}
 
 
+def refine_scene_pose(cfg, data, pred, dev, refiner=None, log=print):
+    """--refine_pose for one scene: the row of refined_metrics_{split}.json.  Target normals from the target block's field when --icp_normals field
+    and its checkpoint is on disk, else by PCA (a printed line says so)."""
+    from dreg_nerf_amd import icp
+    field = None
+    tp = data.get("tgt_nerf_path", "")
+    if cfg.icp_normals == "field" and tp and os.path.exists(tp):
+        from dreg_nerf_amd.visibility import load_block
+        field = load_block(tp, dev)[0]
+        if field.unbounded:
+            field = None
+    row, _ = icp.refine_scene(_points(data, "src"), _points(data, "tgt"), pred["pose"][-1], data["pose"], field, cfg.icp_max_dist, cfg.icp_iters,
+                              refiner=refiner, log=lambda m: log(m, flush=True), scene=str(data["scene"]))
+    return row
+
+
+def write_refined(d, split, rows, refined_rows, log=print):
+    """refined_metrics_{split}.json (ES.summary's schema, fitness and status per scene) and RRE / RTE before and after."""
+    from dreg_nerf_amd import icp
+    out = icp.write_refined_metrics(os.path.join(d, f"refined_metrics_{split}.json"), refined_rows)
+    before = ES.summary({k: rows[k] for k in refined_rows if k in rows})
+    kept = sum(1 for r in refined_rows.values() if r["status"] in (2, 3))
+    log(f"ICP refinement, {len(refined_rows)} scenes ({kept} kept the predicted pose): R_mean {before['R_mean']:.3f} -> {out['R_mean']:.3f} deg, "
+        f"t_mean {before['t_mean']:.4f} -> {out['t_mean']:.4f} -> {d}/refined_metrics_{split}.json", flush=True)
+    return out
+
+
 def init_distributed(local_rank: int):
     """One process per GPU under torch.distributed.run: RCCL ('nccl' on ROCm).  DREG_EVAL_BACKEND=gloo with DREG_EVAL_ONE_GPU=1 is the test hook bench.py
     has too — several ranks on the one GPU of a test box exercise the sharding and the gather (tests/test_hip_eval_pipeline.py); never a measurement."""
@@ -72,7 +99,7 @@ def main():
     ckpt_path = cfg.ckpt_path or os.path.join(cfg.root_dir, "out", cfg.expname, "model.pth")
     if CheckPointManager(verbose=rank == 0).load_no_config(ckpt_path, models={"model": model}, map_location=dev) == 0 and not os.path.exists(ckpt_path):
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
-    rows, fgr_rows = {}, {}
+    rows, fgr_rows, refined_rows = {}, {}, {}
     per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
@@ -110,6 +137,8 @@ def main():
             model.check_inputs()      # a grid with values outside its voxel_mask (the row-list stem would have dropped them) is an error of THESE scenes
             for data, pred in zip(batch, preds):
                 rows[data["scene"]] = _row(LS.evaluate_camera_alignment(pred["pose"][-1], data["pose"]), dt)
+                if cfg.refine_pose:    # the "fine" half: point-to-plane ICP from the predicted pose (refine_registration, global_registration.py:85-93);
+                    refined_rows[data["scene"]] = refine_scene_pose(cfg, data, pred, dev)      # the forward calls and their batches are the unflagged run's
             if not per_scene_extras:
                 continue
             data, pred = batch[0], preds[0]
@@ -141,7 +170,7 @@ def main():
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])
                 fgr_rows[data["scene"]] = {"R_mean": float(e["R_error_mean"]), "t_mean": float(e["t_error_mean"]),
                                            "R_med": float(e["R_error_med"]), "t_med": float(e["t_error_med"]), "time": sec}
-    rows, fgr_rows = ES.gather_rows(rows, world), ES.gather_rows(fgr_rows, world)
+    rows, fgr_rows, refined_rows = ES.gather_rows(rows, world), ES.gather_rows(fgr_rows, world), ES.gather_rows(refined_rows, world)
     if rank == 0:
         out = ES.summary(rows)
         d = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic")
@@ -154,6 +183,8 @@ def main():
             with open(os.path.join(d, f"fgr_metrics_{split}.json"), "w") as f:
                 json.dump(fo, f, indent=4)
             print(f"FGR baseline: R_mean={fo['R_mean']:.3f} deg, t_mean={fo['t_mean']:.4f} -> {d}/fgr_metrics_{split}.json", flush=True)
+        if refined_rows:
+            write_refined(d, split, rows, refined_rows)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -6,7 +6,7 @@ voxel_grid.pt / voxel_mask.pt / voxel_point_cloud.ply and their density_voxel_* 
 The reference's other two jobs, for a scene trained by train_ngp_nerf.py (<root>/<scene> images, <root>/out/<expname>/[block_k/]model.pth), run INSTEAD of
 the extraction when asked for:
 
-    python eval_ngp_nerf.py --dataset objaverse --root_dir <images> --scene <id> --expname <id> [--multi_blocks] --eval_images --point_cloud
+    python eval_ngp_nerf.py --dataset objaverse --root_dir <images> --scene <id> --expname <id> [--multi_blocks] --eval_images --point_cloud [--normals]
 
   --eval_images   evaluate() (:159-244): held-out views rendered over white, PSNR / SSIM by the fused kernel (dreg_nerf_amd/image_metrics.py) ->
                   <root>/eval/<scene>/[block_k/]val/{rgb_test,rgb_gt,inv_depth_test}_i.png and metrics.json (no lpips key: DESIGN.md §3d)
@@ -94,7 +94,7 @@ def evaluate_block(ckpt_path: str, val, scene: str, out_dir: str, dev, views_per
 
 
 @torch.no_grad()
-def generate_point_cloud(ckpt_path: str, K, width: int, height: int, dev, min_depth: float = 2.0, max_depth: float = 6.0):
+def generate_point_cloud(ckpt_path: str, K, width: int, height: int, dev, min_depth: float = 2.0, max_depth: float = 6.0, normals: bool = False):
     """The reference's generate_point_cloud (eval_ngp_nerf.py:246-334): the block rendered over white from every training camera of the checkpoint
     (camera_poses) at the dataset's intrinsics; pixels with min_depth <= depth <= max_depth become points o + d * depth with the rendered colour,
     in camera-then-pixel order, written to point_cloud.ply next to the checkpoint.  Returns the number of points."""
@@ -110,7 +110,10 @@ def generate_point_cloud(ckpt_path: str, K, width: int, height: int, dev, min_de
 
     points, colors = IM.point_cloud_from_views(views(), min_depth, max_depth)
     path = os.path.join(os.path.dirname(ckpt_path), "point_cloud.ply")
-    vis_dump.write_ply(path, points.float().cpu().numpy(), colors.float().cpu().numpy())
+    nrm = None
+    if normals:          # --normals: the field's own surface normals at the points (the density gradient); the file is unchanged without the flag
+        nrm = ngp.field_normals(field, points.float()).cpu().numpy()
+    vis_dump.write_ply(path, points.float().cpu().numpy(), colors.float().cpu().numpy(), nrm)
     print(f"[INFO] Point Cloud Saved to {path}.", flush=True)
     return int(points.shape[0])
 
@@ -162,7 +165,7 @@ def evaluate_scene(cfg, dev):
             res = evaluate_block(path, val, cfg.scene, out_dir, dev)
             print(f"{path}: {len(val)} views, psnr {res[cfg.scene]['psnr']:.3f} ssim {res[cfg.scene]['ssim']:.5f} -> {out_dir}/metrics.json", flush=True)
         if cfg.point_cloud:
-            generate_point_cloud(path, val.K, val.WIDTH, val.HEIGHT, dev)
+            generate_point_cloud(path, val.K, val.WIDTH, val.HEIGHT, dev, normals=cfg.normals)
 
 
 def main():

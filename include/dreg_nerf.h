@@ -799,6 +799,34 @@ size_t dreg_image_metrics_workspace_bytes(int N, int H, int W, int C);
 int dreg_image_metrics(const float* pred, const float* gt, int N, int H, int W, int C, const float* taps, float* ssim, float* mse, float* psnr,
                        float* ssim_map, uint8_t* pred_u8, uint8_t* gt_u8, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- density of a NeRF block with its gradient
+ * (csrc/ngp_grad.hip; rule: DESIGN.md §3f) x, table, w1, w2, the five level arrays and aabb as for dreg_ngp_density_fwd.  density fp32 [Np] equals
+ * dreg_ngp_density_fwd_ws's bit for bit; grad fp32 [Np,3] = d density / d x in world space, the straight-through gradient of the field (fp16
+ * roundings taken as identity; piecewise constant per hash-grid cell times the density), exactly zero where x is not strictly inside the aabb;
+ * relu_mask (optional, null = not written) uint64 [Np]: bit j set when hidden unit j of the density net is active at the point.
+ * contract != 0 (unbounded scenes), Np < 0 or a null required pointer: DREG_EINVAL before any launch; Np == 0: nothing is launched. */
+int dreg_ngp_density_grad(const float* x, const void* table, const void* w1, const void* w2, float* density, float* grad, unsigned long long* relu_mask,
+                          const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                          const float* aabb, int Np, int contract, void* stream);
+
+/* ---------------------------------------------------------------------------------------------- point-to-plane ICP refinement of a pose
+ * (csrc/icp.hip; rule: DESIGN.md §3f; the reference's refine_registration, conerf/geometry/global_registration.py:85-93) for ONE pair per call.
+ * src fp32 [Ns,3].  The target comes sorted by the cells of a uniform grid (dreg_nerf_amd/icp.py TargetIndex): tgt_points / tgt_normals fp32
+ * [Nt,3] in sorted order, perm int32 [Nt] = the caller's index of each sorted point, cell_start int32 [nx*ny*nz + 1], cell id = ix + nx*(iy + ny*iz),
+ * ix = floor((x - grid_lo[0]) / cell) in fp32; grid_lo: 3 fp32 in HOST memory; cell >= max_dist; nx*ny*nz <= 2^24.  A zero normal excludes its point.
+ * pose fp64 [12] on the device (R row-major, then t), refined in place: `iters` times the correspondence kernel and the 6x6 solve, 2*iters launches
+ * on `stream`, no host synchronisation, no readback, no atomics (bit-identical between runs).  stats fp64 [iters,7] on the device: per iteration
+ * count, sum e^2, sum d^2, |omega|, |v|, the smallest Cholesky pivot ratio d_k^2 / A_kk, status (0 running, 1 converged: |omega| < tol_rot and
+ * |v| < tol_trans, 2 fewer than 6 correspondences, 3 a pivot ratio <= eps_cond).  Status 2 / 3 leave the pose untouched; after any non-zero status
+ * the remaining rows repeat that row.  Optional device outputs (null = not written), as of the last iteration that ran: sums fp64 [30] (the 21
+ * upper-triangle entries of J^T J row-major, the 6 of J^T e, sum e^2, sum d^2, count), corr int32 [Ns] (caller's target index, -1 = none), dist2 fp32
+ * [Ns] (squared distance of the correspondence, +inf for none).  workspace: dreg_icp_workspace_bytes(Ns, iters) bytes of device memory, 8-byte aligned. */
+size_t dreg_icp_workspace_bytes(int Ns, int iters);
+int dreg_icp_refine(const float* src, int Ns, const float* tgt_points, const float* tgt_normals, const int* perm, const int* cell_start, int Nt,
+                    const float* grid_lo, float cell, int nx, int ny, int nz, double* pose, float max_dist, int iters,
+                    double tol_rot, double tol_trans, double eps_cond, double* stats, double* sums, int* corr, float* dist2,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
