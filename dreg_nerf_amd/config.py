@@ -63,6 +63,14 @@ def config_parser(argv=None):
     p.add_argument("--icp_iters", type=int, default=30, help="--refine_pose: iteration limit")
     p.add_argument("--icp_normals", type=str, default="field", choices=["field", "pca"],
                    help="--refine_pose: target normals from the target block's density gradient (needs the block's checkpoint, else PCA) or by neighbourhood PCA")
+    p.add_argument("--ransac_pose", action="store_true",
+                   help="eval_nerf_regtr.py: also estimate every pose robustly from the predicted correspondences (fused RANSAC kernels + consensus refits, "
+                        "DESIGN.md 3g) and write ransac_metrics_{split}.json next to metrics_{split}.json, which is unchanged; with --refine_pose ICP is run "
+                        "from that pose as well (ransac_refined_metrics_{split}.json)")
+    p.add_argument("--ransac_thresh", type=float, default=0.05, help="--ransac_pose: inlier distance (round 0's voxel-average cell and ICP's default gate; not tuned)")
+    p.add_argument("--ransac_hyps", type=int, default=16384, help="--ransac_pose: number of minimal-sample hypotheses")
+    p.add_argument("--ransac_seed", type=int, default=0, help="--ransac_pose: seed of the triplet draw")
+    p.add_argument("--ransac_min_overlap", type=float, default=0.0, help="--ransac_pose: drop correspondences whose predicted overlap score is below this")
     p.add_argument("--normals", action="store_true",
                    help="eval_ngp_nerf.py --point_cloud: also write the field's normals (-grad density, normalised) at the points into point_cloud.ply")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")

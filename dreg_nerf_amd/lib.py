@@ -256,6 +256,10 @@ SIGNATURES = {
     # icp.hip
     "dreg_icp_workspace_bytes": (Z, [I, I]),
     "dreg_icp_refine": (I, [P, I, P, P, P, P, I, P, F, I, I, I, P, F, I] + [ctypes.c_double] * 3 + [P, P, P, P, P, Z, P]),
+    # pose_ransac.hip
+    "dreg_pose_ransac_workspace_bytes": (Z, [I, I]),
+    "dreg_pose_ransac": (I, [P, P, I, P, I, F, F, P, Z, P, P, P, P, P, P, P]),
+    "dreg_pose_inliers": (I, [P, P, I, P, F, P, P, P]),
 }
 
 

@@ -63,6 +63,29 @@ def write_refined(d, split, rows, refined_rows, log=print):
     return out
 
 
+def ransac_scene_pose(cfg, data, pred, estimator=None):
+    """--ransac_pose for one scene: (row of ransac_metrics_{split}.json, pose [1,3,4]) from the last layer's predicted correspondences (fused
+    RANSAC kernels + consensus refits).  A scene without a valid hypothesis (status 2) keeps the predicted pose."""
+    from dreg_nerf_amd import pose_ransac
+    return pose_ransac.ransac_scene(pred, data["pose"], cfg.ransac_thresh, cfg.ransac_hyps, cfg.ransac_seed, cfg.ransac_min_overlap, estimator=estimator)
+
+
+def write_ransac(d, split, rows, ransac_rows, ransac_refined_rows=None, log=print):
+    """ransac_metrics_{split}.json (ES.summary's schema; inliers, inlier_ratio and status per scene), with --refine_pose also
+    ransac_refined_metrics_{split}.json, and RRE / RTE of the Kabsch pose against the RANSAC pose."""
+    from dreg_nerf_amd import icp, pose_ransac
+    out = pose_ransac.write_ransac_metrics(os.path.join(d, f"ransac_metrics_{split}.json"), ransac_rows)
+    before = ES.summary({k: rows[k] for k in ransac_rows if k in rows})
+    kept = sum(1 for r in ransac_rows.values() if r["status"] == 2)
+    log(f"RANSAC pose, {len(ransac_rows)} scenes ({kept} kept the predicted pose): Kabsch R_mean {before['R_mean']:.3f} deg, t_mean {before['t_mean']:.4f} | "
+        f"RANSAC R_mean {out['R_mean']:.3f} deg, t_mean {out['t_mean']:.4f} -> {d}/ransac_metrics_{split}.json", flush=True)
+    if ransac_refined_rows:
+        ro = icp.write_refined_metrics(os.path.join(d, f"ransac_refined_metrics_{split}.json"), ransac_refined_rows)
+        log(f"ICP from the RANSAC pose, {len(ransac_refined_rows)} scenes: R_mean {ro['R_mean']:.3f} deg, t_mean {ro['t_mean']:.4f} "
+            f"-> {d}/ransac_refined_metrics_{split}.json", flush=True)
+    return out
+
+
 def init_distributed(local_rank: int):
     """One process per GPU under torch.distributed.run: RCCL ('nccl' on ROCm).  DREG_EVAL_BACKEND=gloo with DREG_EVAL_ONE_GPU=1 is the test hook bench.py
     has too — several ranks on the one GPU of a test box exercise the sharding and the gather (tests/test_hip_eval_pipeline.py); never a measurement."""
@@ -100,6 +123,7 @@ def main():
     if CheckPointManager(verbose=rank == 0).load_no_config(ckpt_path, models={"model": model}, map_location=dev) == 0 and not os.path.exists(ckpt_path):
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows, refined_rows = {}, {}, {}
+    ransac_rows, ransac_refined_rows = {}, {}
     per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
@@ -139,6 +163,10 @@ def main():
                 rows[data["scene"]] = _row(LS.evaluate_camera_alignment(pred["pose"][-1], data["pose"]), dt)
                 if cfg.refine_pose:    # the "fine" half: point-to-plane ICP from the predicted pose (refine_registration, global_registration.py:85-93);
                     refined_rows[data["scene"]] = refine_scene_pose(cfg, data, pred, dev)      # the forward calls and their batches are the unflagged run's
+                if cfg.ransac_pose:    # the robust estimate from the same prediction's correspondences; nothing above reads it
+                    ransac_rows[data["scene"]], rp = ransac_scene_pose(cfg, data, pred)
+                    if cfg.refine_pose:
+                        ransac_refined_rows[data["scene"]] = refine_scene_pose(cfg, data, {"pose": rp[None]}, dev)
             if not per_scene_extras:
                 continue
             data, pred = batch[0], preds[0]
@@ -171,6 +199,8 @@ def main():
                 fgr_rows[data["scene"]] = {"R_mean": float(e["R_error_mean"]), "t_mean": float(e["t_error_mean"]),
                                            "R_med": float(e["R_error_med"]), "t_med": float(e["t_error_med"]), "time": sec}
     rows, fgr_rows, refined_rows = ES.gather_rows(rows, world), ES.gather_rows(fgr_rows, world), ES.gather_rows(refined_rows, world)
+    if cfg.ransac_pose:
+        ransac_rows, ransac_refined_rows = ES.gather_rows(ransac_rows, world), ES.gather_rows(ransac_refined_rows, world)
     if rank == 0:
         out = ES.summary(rows)
         d = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic")
@@ -185,6 +215,8 @@ def main():
             print(f"FGR baseline: R_mean={fo['R_mean']:.3f} deg, t_mean={fo['t_mean']:.4f} -> {d}/fgr_metrics_{split}.json", flush=True)
         if refined_rows:
             write_refined(d, split, rows, refined_rows)
+        if ransac_rows:
+            write_ransac(d, split, rows, ransac_rows, ransac_refined_rows)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

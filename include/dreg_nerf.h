@@ -827,6 +827,22 @@ int dreg_icp_refine(const float* src, int Ns, const float* tgt_points, const flo
                     double tol_rot, double tol_trans, double eps_cond, double* stats, double* sums, int* corr, float* dist2,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- robust pose from correspondences (RANSAC)
+ * (csrc/pose_ransac.hip; rule and fp32 operation order: DESIGN.md §3g) for ONE pair per call.  a, b fp32 [N,3]: points of the source frame and
+ * their matches in the target frame; triplets int32 [H,3]: the minimal sample of each hypothesis.  A hypothesis is invalid when two of its
+ * indices are equal, one is outside [0,N), or its triangle is degenerate in a or in b (|e1 x e2|^2 <= eps_area |e1|^2 |e2|^2); otherwise its
+ * pose is the triad of the two triangles and its score the number of correspondences with |R a + t - b|^2 <= thresh * thresh (fp32 throughout).
+ * best int32 [2] = (index, count) of the largest score, the smallest index on a tie; pose fp32 [12] (R row-major, then t) = that hypothesis's
+ * pose; status int32 [1]: 0 found, 2 no valid hypothesis (also N < 3): best = (-1, 0) and pose is NOT written.  Optional device outputs (null =
+ * not written): counts int32 [H] and poses fp32 [H,12] per hypothesis (zeros for an invalid one), mask uint8 [N] = the inliers of the returned
+ * pose (all zero with status 2).  Two or three launches on `stream`, no host synchronisation, no atomics, integer scores: bit-identical between
+ * runs.  workspace: dreg_pose_ransac_workspace_bytes(N, H) bytes of device memory, 4-byte aligned (0 is returned for N < 0 or H <= 0).
+ * dreg_pose_inliers: mask uint8 [N] and count int32 [1] of a pose fp32 [12] that is on the device, by the same arithmetic; one launch. */
+size_t dreg_pose_ransac_workspace_bytes(int N, int H);
+int dreg_pose_ransac(const float* a, const float* b, int N, const int* triplets, int H, float thresh, float eps_area, void* workspace,
+                     size_t workspace_bytes, int* best, float* pose, int* status, int* counts, float* poses, unsigned char* mask, void* stream);
+int dreg_pose_inliers(const float* a, const float* b, int N, const float* pose, float thresh, unsigned char* mask, int* count, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
