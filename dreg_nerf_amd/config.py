@@ -73,6 +73,17 @@ def config_parser(argv=None):
     p.add_argument("--ransac_min_overlap", type=float, default=0.0, help="--ransac_pose: drop correspondences whose predicted overlap score is below this")
     p.add_argument("--normals", action="store_true",
                    help="eval_ngp_nerf.py --point_cloud: also write the field's normals (-grad density, normalised) at the points into point_cloud.ply")
+    p.add_argument("--mesh", action="store_true",
+                   help="eval_ngp_nerf.py: instead of the grid extraction, write mesh.ply next to every block's model.pth: the iso-surface of the block's density "
+                        "at --mesh_level by the fused marching-cubes kernels (DESIGN.md 3h; the reference's convert_sdf_samples_to_ply, utils.py:284-344), with the "
+                        "field's normals and mean colours; prints V, F, area and volume")
+    p.add_argument("--mesh_resolution", type=int, default=256, help="--mesh / --merged_mesh: cells per axis of the lattice that spans the block's aabb")
+    p.add_argument("--mesh_level", type=float, default=None,
+                   help="--mesh / --merged_mesh: density of the iso-surface (default 0.7, the grid extraction's density mask; whether that gives the best-looking "
+                        "surface on trained scenes has not been measured)")
+    p.add_argument("--merged_mesh", action="store_true",
+                   help="eval_nerf_regtr.py: per scene whose block checkpoints are on disk, write merged_mesh_pred.ply and merged_mesh_gt.ply: the source block's mesh "
+                        "moved by the predicted / the known pose, concatenated with the target block's")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

@@ -260,6 +260,11 @@ SIGNATURES = {
     "dreg_pose_ransac_workspace_bytes": (Z, [I, I]),
     "dreg_pose_ransac": (I, [P, P, I, P, I, F, F, P, Z, P, P, P, P, P, P, P]),
     "dreg_pose_inliers": (I, [P, P, I, P, F, P, P, P]),
+    # marching_cubes.hip
+    "dreg_mc_table": (I, [P, P]),
+    "dreg_mc_workspace_bytes": (Z, [I, I, I]),
+    "dreg_mc_count": (I, [P, I, I, I, F, P, Z, P, P]),
+    "dreg_mc_emit": (I, [P, I, I, I, F, P, P, P, Z, P, P, I, I, P]),
 }
 
 

@@ -11,9 +11,8 @@ import numpy as np
 import torch
 
 
-def write_ply(path: str, xyz, rgb=None, normals=None) -> None:
-    """xyz [N,3] float; rgb [N,3] in [0,1] (open3d's colour convention) or None; normals [N,3] or None (double nx / ny / nz after the position,
-    where open3d's writer puts them).  Without normals the file is what it was before the argument existed, byte for byte."""
+def _vertex_block(xyz, rgb=None, normals=None):
+    """(n, header property lines, body bytes) of a vertex element: double x / y / z, then double nx / ny / nz, then uchar red / green / blue."""
     xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
     n = xyz.shape[0]
     props = "property double x\nproperty double y\nproperty double z\n"
@@ -38,10 +37,56 @@ def write_ply(path: str, xyz, rgb=None, normals=None) -> None:
         body = rec.tobytes()
     else:
         body = xyz.astype("<f8").tobytes()
+    return n, props, body
+
+
+def write_ply(path: str, xyz, rgb=None, normals=None) -> None:
+    """xyz [N,3] float; rgb [N,3] in [0,1] (open3d's colour convention) or None; normals [N,3] or None (double nx / ny / nz after the position,
+    where open3d's writer puts them).  Without normals the file is what it was before the argument existed, byte for byte."""
+    n, props, body = _vertex_block(xyz, rgb, normals)
     with open(path, "wb") as f:
         f.write((f"ply\nformat binary_little_endian 1.0\ncomment Created by dreg_nerf_amd (open3d point-cloud layout)\n"
                  f"element vertex {n}\n{props}end_header\n").encode("ascii"))
         f.write(body)
+
+
+def write_mesh_ply(path: str, verts, faces, rgb=None, normals=None) -> None:
+    """A triangle mesh: the vertex element exactly as write_ply writes it (double x / y / z, optional double normals, optional uchar colours from
+    rgb in [0,1]), then `element face` with `property list uchar int vertex_indices` (a count byte 3 and three little-endian int32 per face).
+    Binary little-endian; what MeshLab, Blender and open3d.io.read_triangle_mesh read."""
+    n, props, body = _vertex_block(verts, rgb, normals)
+    faces = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3))
+    assert faces.size == 0 or (faces.min() >= 0 and faces.max() < n), "face index outside the vertex list"
+    rec = np.empty(faces.shape[0], dtype=[("k", "u1"), ("v", "<i4", 3)])
+    rec["k"] = 3
+    rec["v"] = faces
+    with open(path, "wb") as f:
+        f.write((f"ply\nformat binary_little_endian 1.0\ncomment Created by dreg_nerf_amd (triangle mesh)\n"
+                 f"element vertex {n}\n{props}element face {faces.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii"))
+        f.write(body)
+        f.write(rec.tobytes())
+
+
+def read_mesh_ply(path: str):
+    """Reader for write_mesh_ply's files (tests): (verts float64 [V,3], faces int32 [F,3], rgb uint8 [V,3] or None, normals float64 [V,3] or None)."""
+    with open(path, "rb") as f:
+        header = b""
+        while not header.endswith(b"end_header\n"):
+            header += f.readline()
+        lines = header.decode("ascii").splitlines()
+        n = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
+        nf = int([l for l in lines if l.startswith("element face")][0].split()[-1])
+        assert "property list uchar int vertex_indices" in lines
+        has_n = "property double nx" in lines
+        has_c = "property uchar red" in lines
+        vdt = np.dtype([("p", "<f8", 3)] + ([("n", "<f8", 3)] if has_n else []) + ([("c", "u1", 3)] if has_c else []))
+        fdt = np.dtype([("k", "u1"), ("v", "<i4", 3)])
+        data = f.read()
+        assert len(data) == n * vdt.itemsize + nf * fdt.itemsize, "file length does not match its header"
+        v = np.frombuffer(data, dtype=vdt, count=n)
+        fc = np.frombuffer(data, dtype=fdt, count=nf, offset=n * vdt.itemsize)
+        assert (fc["k"] == 3).all()
+        return v["p"].copy(), fc["v"].copy(), (v["c"].copy() if has_c else None), (v["n"].copy() if has_n else None)
 
 
 def read_ply_normals(path: str):

@@ -2,7 +2,8 @@
 """Evaluate NeRF registration on MI355X — drop-in for the metric part of the reference's eval_nerf_regtr.py
 (:224-301; with --dump_outputs also its per-scene transformation_est.json and PLY point clouds, :313-438; with --render_views the renders of
 both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369; with --render_merged, which the reference lacks,
-both blocks rendered as one scene under the ground-truth and the predicted pose and merged_metrics.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+both blocks rendered as one scene under the ground-truth and the predicted pose and merged_metrics.json; with --merged_mesh the two
+blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / merged_mesh_gt.ply): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -124,7 +125,7 @@ def main():
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows, refined_rows = {}, {}, {}
     ransac_rows, ransac_refined_rows = {}, {}
-    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged
+    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged or cfg.merged_mesh
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
     # whatever the rank count — the gathered metrics file does not depend on the sharding (dreg_nerf_amd/eval_shard.py)
@@ -193,6 +194,15 @@ def main():
                     print(f"{data['scene']}: merged render, aligned vs gt PSNR {mm['psnr_mean']:.2f} dB, SSIM {mm['ssim_mean']:.4f}", flush=True)
                 else:
                     print(f"{data['scene']}: no NeRF blocks on disk, merged scene not rendered", flush=True)
+            if cfg.merged_mesh:    # both blocks' surfaces in the target frame under the predicted and the known pose (same pose conventions and skip rule as --render_merged)
+                sp, tp = data.get("src_nerf_path", ""), data.get("tgt_nerf_path", "")
+                if sp and tp and os.path.exists(sp) and os.path.exists(tp):
+                    from dreg_nerf_amd.mesh import merged_scene_mesh
+                    mm = merged_scene_mesh(scene_dir, sp, tp, data["pose"][0], pred["pose"][-1][0], dev, cfg.mesh_resolution, cfg.mesh_level)
+                    print(f"{data['scene']}: merged mesh, source V {mm['src']['verts'].shape[0]} F {mm['src']['faces'].shape[0]}, target V {mm['tgt']['verts'].shape[0]} "
+                          f"F {mm['tgt']['faces'].shape[0]} -> {scene_dir}/merged_mesh_{{pred,gt}}.ply", flush=True)
+                else:
+                    print(f"{data['scene']}: no NeRF blocks on disk, merged mesh not written", flush=True)
             if cfg.fgr_baseline:   # the reference's baseline on the two voxel point clouds (global_registration.py:96-116)
                 T, sec = fgr.run_registration(_points(data, "src"), _points(data, "tgt"))
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])

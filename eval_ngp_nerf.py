@@ -10,7 +10,11 @@ the extraction when asked for:
 
   --eval_images   evaluate() (:159-244): held-out views rendered over white, PSNR / SSIM by the fused kernel (dreg_nerf_amd/image_metrics.py) ->
                   <root>/eval/<scene>/[block_k/]val/{rgb_test,rgb_gt,inv_depth_test}_i.png and metrics.json (no lpips key: DESIGN.md §3d)
-  --point_cloud   generate_point_cloud() (:246-334): depth-range points of the training cameras -> point_cloud.ply next to the checkpoint"""
+  --point_cloud   generate_point_cloud() (:246-334): depth-range points of the training cameras -> point_cloud.ply next to the checkpoint
+
+and, which the reference does on the host with skimage (utils.py:284-344, convert_sdf_samples_to_ply), for the blocks the extraction would visit (or --ckpt_path):
+
+  --mesh [--mesh_resolution 256] [--mesh_level L]   the block's density iso-surface by the fused marching-cubes kernels -> mesh.ply next to the checkpoint"""
 import glob
 import os
 
@@ -168,11 +172,24 @@ def evaluate_scene(cfg, dev):
             generate_point_cloud(path, val.K, val.WIDTH, val.HEIGHT, dev, normals=cfg.normals)
 
 
+def mesh_checkpoints(cfg):
+    """The checkpoints --mesh visits: --ckpt_path when given; else the registration layout the extraction reads; else the trainer's layout."""
+    if cfg.ckpt_path:
+        return [cfg.ckpt_path]
+    found = sorted(glob.glob(os.path.join(cfg.root_dir, cfg.dataset, "nerf_models", cfg.scene or "*", "block_*", "model.pth")))
+    return found or [p for _, p in block_checkpoints(cfg)[0] if os.path.exists(p)]
+
+
 def main():
     cfg = config_parser()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", cfg.local_rank)))
     torch.cuda.set_device(dev)
+    if cfg.mesh:                                 # surface meshes INSTEAD of the extraction; blocks round-robin over the ranks, as the extraction
+        from dreg_nerf_amd import mesh
+        for path in [p for i, p in enumerate(mesh_checkpoints(cfg)) if i % world == rank]:
+            mesh.write_block_mesh(path, dev, cfg.mesh_resolution, cfg.mesh_level, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
+        return
     if cfg.eval_images or cfg.point_cloud:       # image metrics / depth point cloud of one trained scene; the grid extraction below is the default job
         evaluate_scene(cfg, dev)
         return

@@ -843,6 +843,31 @@ int dreg_pose_ransac(const float* a, const float* b, int N, const int* triplets,
                      size_t workspace_bytes, int* best, float* pose, int* status, int* counts, float* poses, unsigned char* mask, void* stream);
 int dreg_pose_inliers(const float* a, const float* b, int N, const float* pose, float thresh, unsigned char* mask, int* count, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- iso-surface of a scalar lattice (marching cubes)
+ * (csrc/marching_cubes.hip; rule, output order and fp32 operation order: DESIGN.md §3h; the reference's convert_sdf_samples_to_ply, utils.py:284-344,
+ * calls skimage's Lewiner variant on the host: parity with it is NOT pinned, on ambiguous configurations the triangulations may differ).
+ * values fp32 [nz,ny,nx] on the device, x fastest; node (ix,iy,iz) sits at origin[c] + (float)i_c * spacing[c]; origin, spacing: 3 fp32 in HOST memory.
+ * A node is inside when value > level (NaN: outside).  A lattice edge from a node to its +x / +y / +z neighbour crosses when exactly one end is
+ * inside and owns ONE vertex: t = (level - v_p) / (v_q - v_p), 0.5 when t is not finite or outside [0,1]; the coordinate along the edge is
+ * origin + ((float)i + t) * spacing, the others origin + (float)j * spacing (fp32, no contraction).  Vertices ascend by owning node
+ * ix + nx*(iy + ny*iz), x- before y- before z-edge; faces ascend by cell (named by its lowest node), table order inside a cell; the right-hand normal
+ * of every face points to the lower values.  The mesh is indexed and, where the surface does not meet the lattice boundary, closed.
+ * dreg_mc_table: the derived triangle table (tools/make_mc_table.py): *width = triangles per row; tris (optional) [256][3 * width] cube edge ids
+ * 4 * axis + k, -1 after a row's last triangle (bit c of the row index: corner (c & 1, c >> 1 & 1, c >> 2 & 1) is inside).  A host function.
+ * dreg_mc_count: three launches (tile pass, two scan kernels), no atomics: counts int32 [2] on the device = (V, F); the workspace keeps one 32-bit
+ * word per node and the prefixes (dreg_mc_workspace_bytes: 4 bytes per node, 8 per (y,z) row, the scan's per-workgroup sums and a 32-byte stamp; 0 for
+ * dimensions that are refused).  The caller reads counts on the host (the one synchronisation), allocates verts fp32 [V,3] and faces int32 [F,3], and
+ * calls dreg_mc_emit with the same values, level and workspace: one launch; none when V = F = 0.  Every index written is bounded by the counts the
+ * workspace holds, whatever `values` contains then.  Identical bytes between runs.
+ * DREG_EINVAL before any launch: a null required pointer, a dimension < 2 or > 1024, more than 2^28 nodes, a workspace that is too small or not
+ * 4-byte aligned, and for emit V, F, the dimensions or level differing from what the count call left in the workspace (emit reads that stamp back:
+ * 32 bytes over `stream`, which the caller's own read of counts has already drained). */
+int dreg_mc_table(signed char* tris, int* width);
+size_t dreg_mc_workspace_bytes(int nx, int ny, int nz);
+int dreg_mc_count(const float* values, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes, int* counts, void* stream);
+int dreg_mc_emit(const float* values, int nx, int ny, int nz, float level, const float* origin, const float* spacing, const void* workspace,
+                 size_t workspace_bytes, float* verts, int* faces, int V, int F, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
