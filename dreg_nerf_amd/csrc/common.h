@@ -54,6 +54,67 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// the same sum for N independent values: the N shuffles of a step are issued together, so a wave that holds several rows pays a step's
+// latency once (each value is added up exactly as wave_sum adds it)
+template <int N>
+__device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        float w[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) w[n] = __shfl_xor(v[n], o, 64);
+#pragma unroll
+        for (int n = 0; n < N; ++n) v[n] += w[n];
+    }
+}
+
+// LayerNorm of N 256-channel rows held by one wave (lane l: channels 4l .. 4l + 3 of every row; g / b: the lane's gamma / beta): the row
+// arithmetic of layernorm_fwd_kernel (pointset.hip, N = 1) and of the row-panel kernel (pointset_panel.hip, N = 8), stated once so that
+// the two agree bit for bit
+template <int N>
+__device__ __forceinline__ void ln_rows_fwd(const float4 (&v)[N], const float4 g, const float4 b, float eps, float (&o)[N][4], float (&mean)[N], float (&rstd)[N]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) mean[n] = v[n].x + v[n].y + v[n].z + v[n].w;
+    wave_sum_n(mean);
+    float d[N][4], var[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        mean[n] = mean[n] * (1.f / 256.f);
+        d[n][0] = v[n].x - mean[n]; d[n][1] = v[n].y - mean[n]; d[n][2] = v[n].z - mean[n]; d[n][3] = v[n].w - mean[n];
+        var[n] = d[n][0] * d[n][0] + d[n][1] * d[n][1] + d[n][2] * d[n][2] + d[n][3] * d[n][3];
+    }
+    wave_sum_n(var);
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        rstd[n] = 1.0f / sqrtf(var[n] * (1.f / 256.f) + eps);
+        o[n][0] = d[n][0] * rstd[n] * g.x + b.x; o[n][1] = d[n][1] * rstd[n] * g.y + b.y; o[n][2] = d[n][2] * rstd[n] * g.z + b.z; o[n][3] = d[n][3] * rstd[n] * g.w + b.w;
+    }
+}
+
+// N rows of the LayerNorm backward, same layout (d: the upstream gradient, v: the forward input, gv: gamma): the normalised input xh (the
+// caller adds d * xh and d to its dgamma / dbeta sums, row by row) and the input gradient o, before any by-passing gradient is added.
+// layernorm_bwd_kernel (N = 1) and the row-panel kernel (N = 8).
+template <int N>
+__device__ __forceinline__ void ln_rows_bwd(const float4 (&v)[N], const float (&d)[N][4], const float (&mean)[N], const float (&rstd)[N], const float (&gv)[4],
+                                            float (&xh)[N][4], float (&o)[N][4]) {
+    float s1[N], s2[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        xh[n][0] = (v[n].x - mean[n]) * rstd[n]; xh[n][1] = (v[n].y - mean[n]) * rstd[n]; xh[n][2] = (v[n].z - mean[n]) * rstd[n]; xh[n][3] = (v[n].w - mean[n]) * rstd[n];
+        s1[n] = 0.f; s2[n] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { s1[n] += d[n][i] * gv[i]; s2[n] += d[n][i] * gv[i] * xh[n][i]; }
+    }
+    wave_sum_n(s1);
+    wave_sum_n(s2);
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        s1[n] = s1[n] * (1.f / 256.f); s2[n] = s2[n] * (1.f / 256.f);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[n][i] = rstd[n] * (d[n][i] * gv[i] - s1[n] - xh[n][i] * s2[n]);
+    }
+}
+
 // Kernel-variant knobs.  The product library (libdreg_nerf_hip.so) has NO process-global mutable state: every knob is a compile-time
 // constant there and its setter does not exist.  The same sources built with -DDREG_PROBE (libdreg_nerf_hip_probe.so, loaded explicitly by
 // tools/ and the variant tests: include/dreg_nerf_probe.h) make them mutable and export the setters.

@@ -28,12 +28,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= N) return;
     const float4 v = *reinterpret_cast<const float4*>(x + (size_t)row * 256 + lane * 4);
-    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.f / 256.f);
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    const float var = wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.f / 256.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
     const float4 gg = *reinterpret_cast<const float4*>(g + lane * 4), bb = *reinterpret_cast<const float4*>(b + lane * 4);
-    float o[4] = {d0 * rstd * gg.x + bb.x, d1 * rstd * gg.y + bb.y, d2 * rstd * gg.z + bb.z, d3 * rstd * gg.w + bb.w};
+    const float4 v1[1] = {v};
+    float o1[1][4], mean1[1], rstd1[1];
+    ln_rows_fwd<1>(v1, gg, bb, eps, o1, mean1, rstd1);
+    float (&o)[4] = o1[0];
+    const float mean = mean1[0], rstd = rstd1[0];
     if (pe) { const float4 p = *reinterpret_cast<const float4*>(pe + (size_t)row * 256 + lane * 4); o[0] += p.x; o[1] += p.y; o[2] += p.z; o[3] += p.w; }
     st4(y + (size_t)row * 256 + lane * 4, o);
     if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
@@ -99,14 +99,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         for (int u = 0; u < U; ++u) {
             const int row = rb + 4 * u;
             if (row < rend) {
-                const float xh[4] = {(v[u].x - mean[u]) * rstd[u], (v[u].y - mean[u]) * rstd[u], (v[u].z - mean[u]) * rstd[u], (v[u].w - mean[u]) * rstd[u]};
-                float s1 = 0.f, s2 = 0.f;
+                const float4 v1[1] = {v[u]};
+                const float d1[1][4] = {{d[u][0], d[u][1], d[u][2], d[u][3]}}, m1[1] = {mean[u]}, r1[1] = {rstd[u]};
+                float xh[1][4], o1[1][4];
+                ln_rows_bwd<1>(v1, d1, m1, r1, gv, xh, o1);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { s1 += d[u][i] * gv[i]; s2 += d[u][i] * gv[i] * xh[i]; dg[i] += d[u][i] * xh[i]; db[i] += d[u][i]; }
-                s1 = wave_sum(s1) * (1.f / 256.f); s2 = wave_sum(s2) * (1.f / 256.f);
-                float o[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = rstd[u] * (d[u][i] * gv[i] - s1 - xh[i] * s2);
+                for (int i = 0; i < 4; ++i) { dg[i] += d[u][i] * xh[0][i]; db[i] += d[u][i]; }
+                float (&o)[4] = o1[0];
                 if (dx_add) { o[0] += old[u].x; o[1] += old[u].y; o[2] += old[u].z; o[3] += old[u].w; }
                 if (dx_add2) { o[0] += old2[u].x; o[1] += old2[u].y; o[2] += old2[u].z; o[3] += old2[u].w; }
                 *reinterpret_cast<float4*>(dx + (size_t)row * 256 + lane * 4) = make_float4(o[0], o[1], o[2], o[3]);

@@ -63,6 +63,7 @@ struct Ps {
     Lin lin[NLIN];
     Layout lay;
     int fuse = 1;
+    int panel = 2;         // with fuse: the row-local chains between attention calls as row-panel launches (pointset_panel.hip, bit-identical): 1 forward, 2 forward and backward
     int group_wgrad = 1;   // with fuse: the linear layers' weight-gradient partials of a backward pass in one launch per tile shape (bit-identical)
     std::vector<hipEvent_t> ev;            // one per linear layer + spares: "its output gradient is complete" (recorded on the caller's stream)
     hipEvent_t ev_done = nullptr;
@@ -73,7 +74,7 @@ struct Ps {
     hipEvent_t ring_ev[RING] = {};
     unsigned ring_next = 0;
     // optional HIP-event brackets around every linear-layer launch (forward / data gradient / weight gradient): dreg_ps_set_timing
-    struct Timed { hipEvent_t e0, e1; int kind, rows, cin, cout, flags; };     // kind 0 fwd, 1 dgrad, 2 wgrad; flags: 1 addend, 2 fp32 output, 4 split-K workspace offered
+    struct Timed { hipEvent_t e0, e1; int kind, rows, cin, cout, flags; };     // kind 0 fwd, 1 dgrad, 2 wgrad, 3 / 4 forward / backward row panel (cin = K1, cout = N2); flags: 1 addend, 2 fp32 output, 4 split-K workspace offered
     bool timing = false;
     std::vector<Timed> timed;
     size_t timed_used = 0;
@@ -218,10 +219,14 @@ void dreg_ps_destroy(void* h)
 // 0: the arithmetic of the per-op path, bit for bit (separate ReLU-mask / gradient-sum / cast launches where that path has them);
 // 1 (default): ReLU mask and the decoder's gradient sum in the data-gradient epilogues, one LayerNorm backward for the final norm's two
 // applications, all bias column sums in one batched launch pair
-void dreg_ps_set_fuse(void* h, int fuse) { ((Ps*)h)->fuse = fuse ? 1 : 0; }
+// 2: 1 + the forward chains out_proj_self -> LN2 -> in_proj_cross, out_proj_cross -> LN3 -> linear1 and linear2 -> next layer's LN1 ->
+// in_proj_self as one row-panel launch each (dreg_ps_panel_fwd);  3 (default; larger values mean 3): 2 + the backward chains dgrad linear1 ->
+// LN3' -> dgrad out_proj_cross, dgrad in_proj_cross -> LN2' -> dgrad out_proj_self and dgrad in_proj_self -> LN1' (dreg_ps_panel_bwd).
+// 1, 2 and 3 are bit-identical.
+void dreg_ps_set_fuse(void* h, int fuse) { ((Ps*)h)->fuse = fuse ? 1 : 0; ((Ps*)h)->panel = fuse >= 3 ? 2 : fuse >= 2 ? 1 : 0; }
 void dreg_ps_set_group_wgrad(void* h, int on) { ((Ps*)h)->group_wgrad = on ? 1 : 0; }   // per handle; read at every backward call
 // HIP events around every linear-layer launch of the following passes (bench.py's bracketed step); read them back AFTER a device
-// synchronisation: info[5 * i] = (kind 0 fwd / 1 dgrad / 2 wgrad, rows, cin, cout, flags: 1 addend, 2 fp32 output, 4 split-K workspace
+// synchronisation: info[5 * i] = (kind 0 fwd / 1 dgrad / 2 wgrad / 3, 4 forward, backward row panel with cin = K1 and cout = N2, rows, cin, cout, flags: 1 addend, 2 fp32 output, 4 split-K workspace
 // offered), ms[i] = the launch's duration.  Returns the number of records (and clears them).
 void dreg_ps_set_timing(void* h, int enable) { ((Ps*)h)->timing = enable != 0; }     // (records stay until they are read)
 int dreg_ps_read_timings(void* h, int* info, float* ms, int cap)
@@ -256,26 +261,53 @@ int dreg_ps_forward(void* h, void* arena, size_t arena_bytes, const int64_t* pac
     const float sc = 0.17677669529663687f;   // 1 / sqrt(256 / 8)
     auto pk = [&](int li, int t) { return (const void*)packs[2 * li + t]; };
     const float* xin = feats;
+    // row-panel launches (under dreg_ps_set_timing a panel is ONE record of kind 3: the bracketed step launches what every step launches)
+    const bool panel = p->fuse && p->panel;
+    auto chain = [&](const void* a1, int li1, int b1, const float* res, float* x, int nw, int nb, const float* pe_, void* hh, float* stt, int li2, int b2,
+                     void* out2, int k1, int n2, int relu) {
+        PsScope sc(p, stream, 3, R, k1, n2, 0);
+        return dreg_ps_panel_fwd(a1, pk(li1, 0), p->val[b1], res, x, p->val[nw], p->val[nb], pe_, hh, stt, pk(li2, 0), p->val[b2], out2, R, k1, n2, relu, 1e-5f, stream);
+    };
     for (int l = 0; l < NL; ++l) {
         const LayerBuf& b = y.L[l];
         const int o = l * PL_COUNT;
         float* xout = (float*)(A + y.allx) + (size_t)l * R * E;
         // self attention: q = k = v = LN1(x) + pe (transformer.py:238-250)
-        CK(dreg_layernorm_fwd(xin, p->val[o + N1W], p->val[o + N1B], pe, A + b.h1, (float*)(A + b.st1), R, E, 1e-5f, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.h1, pk(lin_index(l, LIN_SI), 0), p->val[o + SIB], nullptr, A + b.qkv1, R, E, E3, 0, 0, stream));
+        if (l == 0 || !panel) {                           // (with panels: the previous layer's last chain wrote h1 / st1 / qkv1)
+            CK(dreg_layernorm_fwd(xin, p->val[o + N1W], p->val[o + N1B], pe, A + b.h1, (float*)(A + b.st1), R, E, 1e-5f, 0, stream));
+            CK(linear_fwd(p, y, A, A + b.h1, pk(lin_index(l, LIN_SI), 0), p->val[o + SIB], nullptr, A + b.qkv1, R, E, E3, 0, 0, stream));
+        }
         CK(dreg_mha_varlen_fwd(A + b.qkv1, A + b.qkv1 + E * 2, A + b.qkv1 + 2 * E * 2, A + b.o1, (float*)(A + b.lse1), probs_self, nprob, max_len, max_len,
                                R, NH, E3, E3, E3, E, sc, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.o1, pk(lin_index(l, LIN_SO), 0), p->val[o + SOB], xin, A + b.xa, R, E, E, 0, 1, stream));
         // cross attention: q from a set, k = v from the pair's other set (transformer.py:252-262)
-        CK(dreg_layernorm_fwd((const float*)(A + b.xa), p->val[o + N2W], p->val[o + N2B], pe, A + b.h2, (float*)(A + b.st2), R, E, 1e-5f, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.h2, pk(lin_index(l, LIN_CI), 0), p->val[o + CIB], nullptr, A + b.qkv2, R, E, E3, 0, 0, stream));
+        if (panel) {
+            CK(chain(A + b.o1, lin_index(l, LIN_SO), o + SOB, xin, (float*)(A + b.xa), o + N2W, o + N2B, pe, A + b.h2, (float*)(A + b.st2),
+                     lin_index(l, LIN_CI), o + CIB, A + b.qkv2, E, E3, 0));
+        } else {
+            CK(linear_fwd(p, y, A, A + b.o1, pk(lin_index(l, LIN_SO), 0), p->val[o + SOB], xin, A + b.xa, R, E, E, 0, 1, stream));
+            CK(dreg_layernorm_fwd((const float*)(A + b.xa), p->val[o + N2W], p->val[o + N2B], pe, A + b.h2, (float*)(A + b.st2), R, E, 1e-5f, 0, stream));
+            CK(linear_fwd(p, y, A, A + b.h2, pk(lin_index(l, LIN_CI), 0), p->val[o + CIB], nullptr, A + b.qkv2, R, E, E3, 0, 0, stream));
+        }
         CK(dreg_mha_varlen_fwd(A + b.qkv2, A + b.qkv2 + E * 2, A + b.qkv2 + 2 * E * 2, A + b.o2, (float*)(A + b.lse2), probs_cross, nprob, max_len, max_len,
                                R, NH, E3, E3, E3, E, sc, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.o2, pk(lin_index(l, LIN_CO), 0), p->val[o + COB], A + b.xa, A + b.xb, R, E, E, 0, 1, stream));
         // feed-forward (transformer.py:283-293)
-        CK(dreg_layernorm_fwd((const float*)(A + b.xb), p->val[o + N3W], p->val[o + N3B], nullptr, A + b.h3, (float*)(A + b.st3), R, E, 1e-5f, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.h3, pk(lin_index(l, LIN_1), 0), p->val[o + L1B], nullptr, A + b.f, R, E, FF, 1, 0, stream));
-        CK(linear_fwd(p, y, A, A + b.f, pk(lin_index(l, LIN_2), 0), p->val[o + L2B], A + b.xb, xout, R, FF, E, 0, 1, stream));
+        if (panel) {
+            CK(chain(A + b.o2, lin_index(l, LIN_CO), o + COB, (const float*)(A + b.xa), (float*)(A + b.xb), o + N3W, o + N3B, nullptr, A + b.h3, (float*)(A + b.st3),
+                     lin_index(l, LIN_1), o + L1B, A + b.f, E, FF, 1));
+        } else {
+            CK(linear_fwd(p, y, A, A + b.o2, pk(lin_index(l, LIN_CO), 0), p->val[o + COB], A + b.xa, A + b.xb, R, E, E, 0, 1, stream));
+            CK(dreg_layernorm_fwd((const float*)(A + b.xb), p->val[o + N3W], p->val[o + N3B], nullptr, A + b.h3, (float*)(A + b.st3), R, E, 1e-5f, 0, stream));
+            CK(linear_fwd(p, y, A, A + b.h3, pk(lin_index(l, LIN_1), 0), p->val[o + L1B], nullptr, A + b.f, R, E, FF, 1, 0, stream));
+        }
+        if (panel && l + 1 < NL) {
+            // linear2 -> the next layer's LN1 (+pe) -> its in_proj_self (the last layer's linear2 feeds the final norm: a launch of its own)
+            const LayerBuf& nb = y.L[l + 1];
+            const int no = o + PL_COUNT;
+            CK(chain(A + b.f, lin_index(l, LIN_2), o + L2B, (const float*)(A + b.xb), xout, no + N1W, no + N1B, pe, A + nb.h1, (float*)(A + nb.st1),
+                     lin_index(l + 1, LIN_SI), no + SIB, A + nb.qkv1, FF, E3, 0));
+        } else {
+            CK(linear_fwd(p, y, A, A + b.f, pk(lin_index(l, LIN_2), 0), p->val[o + L2B], A + b.xb, xout, R, FF, E, 0, 1, stream));
+        }
         xin = xout;
     }
     // the shared final norm of the six layer outputs: cond (fp32) and LN(x) + pe (compute dtype) from one read (nerf_regtr.py:170-206)
@@ -333,6 +365,13 @@ int dreg_ps_backward(void* h, void* arena, size_t arena_bytes, const int64_t* pa
     struct GroupRec { char d[160]; int variant, nblocks; };
     std::vector<GroupRec> grp;
     const bool group = fuse && p->group_wgrad && !p->timing;
+    // row-panel launches for the chains around the LayerNorm backward passes (under dreg_ps_set_timing: one record of kind 4 each)
+    const bool panel = fuse && p->panel >= 2;
+    auto panel_bwd = [&](const void* g1, const void* w1t, const float* x, const float* stt, const float* gamma, const float* add, const float* add2, float* dx, void* dx_bf,
+                         float* part, const void* w2t, void* out2, int k1, int n2) {
+        PsScope sc(p, stream, 4, R, k1, n2, 0);
+        return dreg_ps_panel_bwd(g1, w1t, x, stt, gamma, add, add2, dx, dx_bf, part, w2t, out2, R, k1, n2, stream);
+    };
     auto param_grads = [&](int li, const void* g, const void* x, int rows, size_t wg_off, size_t cs_off) -> int {
         const Lin& l = p->lin[li];
         bool grouped = false;
@@ -433,32 +472,55 @@ int dreg_ps_backward(void* h, void* arena, size_t arena_bytes, const int64_t* pa
             CK(dreg_relu_bwd(A + b.f, A + y.dO, A + b.gF, (size_t)R * FF, 0, 0, 0, stream));
         }
         CK(param_grads(lin_index(l, LIN_2), Gbf, A + b.f, R, b.wg[LIN_2], b.cs[LIN_2]));
+        float* Gb = (float*)(A + y.gx[0]);
+        if (panel) {
+            // dgrad linear1 -> LN3 backward (+G) -> dgrad out_proj_cross (cross attention: xb = out_proj(mha(in_proj(LN2(xa) + pe))) + xa)
+            CK(panel_bwd(A + b.gF, pk(lin_index(l, LIN_1), 1), (const float*)(A + b.xb), (const float*)(A + b.st3), p->val[o + N3W], G, nullptr, Gb, A + b.gB,
+                                 (float*)(A + b.lnp[2]), pk(lin_index(l, LIN_CO), 1), A + y.dO, FF, E));
+            CK(param_grads(lin_index(l, LIN_1), A + b.gF, A + b.h3, R, b.wg[LIN_1], b.cs[LIN_1]));
+            ln_rec(b.lnp[2], o + N3W, o + N3B, R);
+        } else {
         CK(linear_dgrad(p, y, A, A + b.gF, pk(lin_index(l, LIN_1), 1), A + y.dH, nullptr, nullptr, R, E, FF, stream));
         CK(param_grads(lin_index(l, LIN_1), A + b.gF, A + b.h3, R, b.wg[LIN_1], b.cs[LIN_1]));
-        float* Gb = (float*)(A + y.gx[0]);
         CK(dreg_layernorm_bwd_parts((const float*)(A + b.xb), A + y.dH, nullptr, p->val[o + N3W], (const float*)(A + b.st3), Gb, G, nullptr, A + b.gB,
                                     (float*)(A + b.lnp[2]), R, E, 0, stream));
         ln_rec(b.lnp[2], o + N3W, o + N3B, R);
         // cross attention: xb = out_proj(mha(in_proj(LN2(xa) + pe))) + xa
         CK(linear_dgrad(p, y, A, A + b.gB, pk(lin_index(l, LIN_CO), 1), A + y.dO, nullptr, nullptr, R, E, E, stream));
+        }
         CK(param_grads(lin_index(l, LIN_CO), A + b.gB, A + b.o2, R, b.wg[LIN_CO], b.cs[LIN_CO]));
         CK(dreg_mha_varlen_bwd(A + b.qkv2, A + b.qkv2 + E * 2, A + b.qkv2 + 2 * E * 2, A + b.o2, A + y.dO, (const float*)(A + b.lse2), (float*)(A + y.dvec),
                                A + b.gQ2, A + b.gQ2 + E * 2, A + b.gQ2 + 2 * E * 2, probs_cross, nprob, max_len, max_len, R, NH, E3, E3, E3, E, sc, 0, stream));
+        float* Ga = (float*)(A + y.gx[1]);
+        if (panel) {
+            // dgrad in_proj_cross -> LN2 backward (+Gb) -> dgrad out_proj_self (self attention: xa = out_proj(mha(in_proj(LN1(x) + pe))) + x)
+            CK(panel_bwd(A + b.gQ2, pk(lin_index(l, LIN_CI), 1), (const float*)(A + b.xa), (const float*)(A + b.st2), p->val[o + N2W], Gb, nullptr, Ga, A + b.gC,
+                                 (float*)(A + b.lnp[1]), pk(lin_index(l, LIN_SO), 1), A + y.dO, E3, E));
+            CK(param_grads(lin_index(l, LIN_CI), A + b.gQ2, A + b.h2, R, b.wg[LIN_CI], b.cs[LIN_CI]));
+            ln_rec(b.lnp[1], o + N2W, o + N2B, R);
+        } else {
         CK(linear_dgrad(p, y, A, A + b.gQ2, pk(lin_index(l, LIN_CI), 1), A + y.dH, nullptr, nullptr, R, E, E3, stream));
         CK(param_grads(lin_index(l, LIN_CI), A + b.gQ2, A + b.h2, R, b.wg[LIN_CI], b.cs[LIN_CI]));
-        float* Ga = (float*)(A + y.gx[1]);
         CK(dreg_layernorm_bwd_parts((const float*)(A + b.xa), A + y.dH, nullptr, p->val[o + N2W], (const float*)(A + b.st2), Ga, Gb, nullptr, A + b.gC,
                                     (float*)(A + b.lnp[1]), R, E, 0, stream));
         ln_rec(b.lnp[1], o + N2W, o + N2B, R);
         // self attention: xa = out_proj(mha(in_proj(LN1(x) + pe))) + x
         CK(linear_dgrad(p, y, A, A + b.gC, pk(lin_index(l, LIN_SO), 1), A + y.dO, nullptr, nullptr, R, E, E, stream));
+        }
         CK(param_grads(lin_index(l, LIN_SO), A + b.gC, A + b.o1, R, b.wg[LIN_SO], b.cs[LIN_SO]));
         CK(dreg_mha_varlen_bwd(A + b.qkv1, A + b.qkv1 + E * 2, A + b.qkv1 + 2 * E * 2, A + b.o1, A + y.dO, (const float*)(A + b.lse1), (float*)(A + y.dvec),
                                A + b.gQ1, A + b.gQ1 + E * 2, A + b.gQ1 + 2 * E * 2, probs_self, nprob, max_len, max_len, R, NH, E3, E3, E3, E, sc, 0, stream));
-        CK(linear_dgrad(p, y, A, A + b.gQ1, pk(lin_index(l, LIN_SI), 1), A + y.dH, nullptr, nullptr, R, E, E3, stream));
+        if (!panel) CK(linear_dgrad(p, y, A, A + b.gQ1, pk(lin_index(l, LIN_SI), 1), A + y.dH, nullptr, nullptr, R, E, E3, stream));
         CK(param_grads(lin_index(l, LIN_SI), A + b.gQ1, A + b.h1, R, b.wg[LIN_SI], b.cs[LIN_SI]));
         // the layer input's gradient: through LN1, the by-passing residual (Ga) and — it is the previous layer's output — the final norm
-        if (l == 0) {
+        if (panel) {
+            // dgrad in_proj_self -> LN1 backward (+Ga [+Gprev in place]); no second GEMM
+            float* Gprev = l == 0 ? d_feats : dallx + (size_t)(l - 1) * R * E;
+            void* Gprev_bf = l == 0 ? nullptr : A + y.dallx_bf + (size_t)(l - 1) * R * E * 2;
+            CK(panel_bwd(A + b.gQ1, pk(lin_index(l, LIN_SI), 1), xin, (const float*)(A + b.st1), p->val[o + N1W], Ga, (l == 0 || last_only) ? nullptr : Gprev, Gprev,
+                                 Gprev_bf, (float*)(A + b.lnp[0]), nullptr, nullptr, E3, 0));
+            if (l > 0) { G = Gprev; Gbf = Gprev_bf; }
+        } else if (l == 0) {
             CK(dreg_layernorm_bwd_parts(xin, A + y.dH, nullptr, p->val[o + N1W], (const float*)(A + b.st1), d_feats, Ga, nullptr, nullptr,
                                         (float*)(A + b.lnp[0]), R, E, 0, stream));
         } else {

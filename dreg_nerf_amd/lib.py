@@ -183,6 +183,8 @@ SIGNATURES = {
     "dreg_ps_set_timing": (None, [P, I]),
     "dreg_ps_read_timings": (I, [P, P, P, I]),
     "dreg_ps_arena_bytes": (Z, [P, I]),
+    "dreg_ps_panel_fwd": (I, [P] * 13 + [I, I, I, I, F, P]),
+    "dreg_ps_panel_bwd": (I, [P] * 12 + [I, I, I, P]),
     "dreg_ps_forward": (I, [P, P, Z, P, P, P, P, P, P, I, I, I, P, P, P, P]),
     "dreg_ps_backward": (I, [P, P, Z, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, I]),
     "dreg_posenc_sine": (I, [P, P, I, F, F, P]),

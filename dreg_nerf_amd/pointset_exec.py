@@ -29,7 +29,12 @@ _LINEARS = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "cross_attn
             "linear1.weight", "linear2.weight")
 
 FUSE = True      # False: the per-op path's arithmetic, bit for bit (tests; dreg_ps_set_fuse)
+PANEL = 3        # with FUSE, the level passed to dreg_ps_set_fuse: 1 = every linear layer and LayerNorm a launch of its own; 2 = the forward pass's row-local chains as row-panel launches; 3 = the backward pass's too (all bit-identical)
 GROUP_WGRAD = True   # False: one weight-gradient launch per linear layer instead of one per tile shape (A/B; dreg_ps_set_group_wgrad, per handle, bit-identical)
+
+
+def _fuse_level() -> int:
+    return 0 if not FUSE else int(PANEL)
 
 
 def param_names():
@@ -66,9 +71,9 @@ class PointSetExecutor:
         self.h = self.lib.dreg_ps_create(tab.ctypes.data)
         if not self.h:
             raise L.DregError("dreg_ps_create failed")
-        self.lib.dreg_ps_set_fuse(self.h, int(FUSE))
+        self.lib.dreg_ps_set_fuse(self.h, _fuse_level())
         self.lib.dreg_ps_set_group_wgrad(self.h, int(GROUP_WGRAD))
-        self._fuse = FUSE
+        self._fuse = _fuse_level()
         self._group = GROUP_WGRAD
         self.device = self.params[0].device
         self.arena = None
@@ -131,7 +136,11 @@ class PointSetExecutor:
         for i in range(n):
             kind, rows, cin, cout, flags = (info[5 * i + k] for k in range(5))
             fl = 2.0 * rows * cin * cout
-            if kind == 2:
+            if kind in (3, 4):   # a row-panel launch (csrc/pointset_panel.hip): GEMM (cin -> 256), row pass, GEMM (256 -> cout)
+                fl = 2.0 * rows * 256 * (cin + cout)
+                name = f"ps_panel_kernel<{'true' if kind == 4 else 'false'}>"
+                label = f"panel {'bwd' if kind == 4 else 'fwd'} B{rows} {cin}->256->{cout}"
+            elif kind == 2:
                 name = ops.wgrad_kernel_name(self.lib, rows, 1, 1, 1, cin, cout, 1)
                 label = f"wgrad B{rows} 1x1x1x{cin} g1x1x1x{cout} k1s1"
             elif kind == 1:     # data gradient: the transposed problem (cout -> cin)
@@ -143,9 +152,9 @@ class PointSetExecutor:
             profiler.add_measured(name, label, fl, ms[i])
 
     def forward(self, feats, xyz, pe, tab):
-        if self._fuse != FUSE:
-            self.lib.dreg_ps_set_fuse(self.h, int(FUSE))
-            self._fuse = FUSE
+        if self._fuse != _fuse_level():
+            self._fuse = _fuse_level()
+            self.lib.dreg_ps_set_fuse(self.h, self._fuse)
         if self._group != GROUP_WGRAD:
             self.lib.dreg_ps_set_group_wgrad(self.h, int(GROUP_WGRAD))
             self._group = GROUP_WGRAD

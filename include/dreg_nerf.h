@@ -902,7 +902,10 @@ int dreg_conv3_brick(const void* in, const void* wpk, void* out, const float* bi
  * gradients are accumulated into the grad pointers; weight / bias gradients run on aux_stream (optional) and the caller joins it with
  * `stream` before reading any gradient.  last_only = 1: g_cond [R,256] / g_corr [R,3] / g_ov [R] are the gradients of the LAST layer's
  * outputs only (what the training losses read: train_nerf_regtr.py:178,195,205-206,214,220); heads, decoder and final norm are then
- * differentiated for that layer's R rows instead of 6R.  dreg_ps_set_fuse(0): the arithmetic of the per-op path, bit for bit (tests). */
+ * differentiated for that layer's R rows instead of 6R.  dreg_ps_set_fuse(h, level): 0 = the arithmetic of the per-op path, bit for bit
+ * (tests); 1 = the fused epilogues and batched tails; 2 = 1 + the forward pass's row-local chains between attention calls as row-panel
+ * launches (dreg_ps_panel_fwd); 3 (default; larger values mean 3) = 2 + the backward pass's (dreg_ps_panel_bwd).  1, 2 and 3 are
+ * bit-identical. */
 int dreg_ps_num_params(void);
 int dreg_ps_num_linears(void);
 void* dreg_ps_create(const int64_t* params);
@@ -910,7 +913,7 @@ void dreg_ps_destroy(void* h);
 void dreg_ps_set_fuse(void* h, int fuse);
 void dreg_ps_set_group_wgrad(void* h, int on);   /* 1 (default, with fuse): the split partials of all linear layers' weight gradients by one launch per tile shape at the end of the backward pass (dreg_wgrad_group_launch); 0: one launch per layer.  Bit-identical.  Per handle. */
 void dreg_ps_set_timing(void* h, int enable);            /* HIP events around every linear-layer launch (forward, data gradient, weight gradient) */
-int dreg_ps_read_timings(void* h, int* info, float* ms, int cap);   /* after a device sync: 5 ints per record (kind, rows, cin, cout, flags) + ms; returns the count */
+int dreg_ps_read_timings(void* h, int* info, float* ms, int cap);   /* after a device sync: 5 ints per record (kind, rows, cin, cout, flags) + ms; returns the count.  kind 0 / 1 / 2: forward / data gradient / weight gradient of a linear layer; 3 / 4: a forward / backward row-panel launch (cin = K1, cout = N2) */
 size_t dreg_ps_arena_bytes(void* h, int R);
 int dreg_ps_forward(void* h, void* arena, size_t arena_bytes, const int64_t* packs, const float* feats, const float* xyz, const float* pe,
                     const int* probs_self, const int* probs_cross, int nprob, int max_len, int R,
@@ -919,6 +922,22 @@ int dreg_ps_backward(void* h, void* arena, size_t arena_bytes, const int64_t* pa
                      const int* probs_self, const int* probs_cross, int nprob, int max_len, int R,
                      const float* cond, const float* corr, const float* ov, const float* g_cond, const float* g_corr, const float* g_ov,
                      float* d_feats, void* stream, void* aux_stream, int last_only);
+/* (csrc/pointset_panel.hip) One launch for a row-local chain of an encoder layer, a workgroup per panel of 64 rows.
+ * Forward:  x_out = a1 W1^T + bias1 + residual (fp32 [R,256]);  h_out = LayerNorm(x_out; gamma, beta, eps) (+ pe, optional) (bf16 [R,256]),
+ *   stats fp32 [R,2] = (mean, rstd);  out2 = h_out W2^T + bias2, ReLU if relu (bf16 [R,N2]).
+ *   a1 bf16 [R,K1]; w1_packed [256][K1], w2_packed [N2][256]: forward packs of dreg_pack_conv_weight (bf16); K1 % 64 == 0, N2 % 256 == 0.
+ *   Every tensor written equals, bit for bit, what dreg_conv3d_igemm_ws -> dreg_layernorm_fwd -> dreg_conv3d_igemm_ws write.
+ * Backward: dH = g1 W1 (rounded to bf16, not written);  dx = (LayerNorm-backward(dH; x, stats, gamma) + dx_add) + dx_add2 (fp32 [R,256];
+ *   both addends optional, either may be dx itself), dx_bf16 (optional) its bf16 copy, part the dgamma / dbeta partials per 16 rows
+ *   (dreg_layernorm_bwd_workspace_bytes(R), for dreg_layernorm_bwd_final_batched);  out2 = dx_bf16 W2 (bf16 [R,256]) when N2 == 256,
+ *   nothing when N2 == 0.  g1 bf16 [R,K1]; w1t_packed [256][K1], w2t_packed [256][256]: data-gradient packs.  Equal, bit for bit, to
+ *   dreg_conv3d_igemm_ws (transposed) -> dreg_layernorm_bwd_parts -> dreg_conv3d_igemm_ws (transposed). */
+int dreg_ps_panel_fwd(const void* a1, const void* w1_packed, const float* bias1, const float* residual, float* x_out,
+                      const float* gamma, const float* beta, const float* pe, void* h_out, float* stats,
+                      const void* w2_packed, const float* bias2, void* out2, int R, int K1, int N2, int relu, float eps, void* stream);
+int dreg_ps_panel_bwd(const void* g1, const void* w1t_packed, const float* x, const float* stats, const float* gamma,
+                      const float* dx_add, const float* dx_add2, float* dx, void* dx_bf16, float* part,
+                      const void* w2t_packed, void* out2, int R, int K1, int N2, void* stream);
 
 #ifdef __cplusplus
 }

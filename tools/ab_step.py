@@ -1,8 +1,8 @@
 """A/B of one switch on the whole training step, alternating the values inside one process so that clock / thermal drift cancels.
 The switch is either a creation option of the trunk executor (dreg_exec_opts of include/dreg_nerf.h: `opt:sparse_stem`), the point-set executor's
-per-handle `ps:group_wgrad`, or a process-global kernel-variant setter of the MEASUREMENT build (include/dreg_nerf_probe.h: `dreg_conv_set_narrow_small`),
+per-handle `ps:group_wgrad` / `ps:panel` (pointset_exec.PANEL: the level of dreg_ps_set_fuse), or a process-global kernel-variant setter of the MEASUREMENT build (include/dreg_nerf_probe.h: `dreg_conv_set_narrow_small`),
 in which case the whole run uses libdreg_nerf_hip_probe.so.
-usage: python tools/ab_step.py opt:sparse_stem 0 1 | ps:group_wgrad 0 1 | dreg_conv_set_narrow_small 0 1 2 [--dense] [--rounds 3] [--steps 12]"""
+usage: python tools/ab_step.py opt:sparse_stem 0 1 | ps:group_wgrad 0 1 | ps:panel 1 3 | dreg_conv_set_narrow_small 0 1 2 [--dense] [--rounds 3] [--steps 12]"""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +22,8 @@ if setter.startswith("opt:"):
     def fn(v): trunk_exec.OPTS[setter[4:]] = v
 elif setter == "ps:group_wgrad":
     def fn(v): pointset_exec.GROUP_WGRAD = bool(v)
+elif setter == "ps:panel":
+    def fn(v): pointset_exec.PANEL = v
 elif setter == "aux:cumask":      # 0 = the default low-priority second stream; 1..7 = CU masks of trunk_exec.aux_stream
     def fn(v):
         trunk_exec.AUX_CU_MASK = v
