@@ -135,8 +135,10 @@ __global__ __launch_bounds__(256) void infonce_nn_kernel(const float* __restrict
         if (b2 < best || (b2 == best && j2 < bj)) { best = b2; bj = j2; }
     }
     if (lane == 0) {
-        nn[wv] = bj;
-        const float m = sqrtf(best) < r_p ? 1.f : 0.f;
+        // no distance compared below the start value (non-finite coordinates): neighbour 0, no positive — infonce_rows_kernel reads lg[nn]
+        const bool none = (unsigned)bj >= (unsigned)nt;
+        nn[wv] = none ? 0 : bj;
+        const float m = (!none && sqrtf(best) < r_p) ? 1.f : 0.f;
         mask[wv] = m;
         // the pair's positive count is summed by infonce_count_kernel: 4,876 float atomics on four addresses were most of this kernel
     }

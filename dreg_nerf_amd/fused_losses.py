@@ -3,6 +3,7 @@ torch kernels per pair).  Reference: train_nerf_regtr.py:186-229, conerf/loss/co
 conerf/loss/feature_loss.py:24-73; dreg_nerf_amd/losses.py keeps the per-pair torch formulation (evaluation, tests)."""
 import ctypes
 import struct
+import weakref
 
 import torch
 
@@ -13,8 +14,9 @@ _WSYM = {}
 
 
 def _wsym(W):
-    """triu(W) + triu(W)^T, cached against W's storage, its version counter and the optimizer generation (FlatAdamW writes parameters behind torch's
-    version counters; the reference never optimises W — feature_loss.py quirk Q5 — so in training this is one tiny launch per optimizer step)."""
+    """triu(W) + triu(W)^T, cached against the tensor object W (a weak reference: the address and the version counter of a freed parameter come back
+    in the next one allocated), its version counter and the optimizer generation (FlatAdamW writes parameters behind torch's version counters; the
+    reference never optimises W — feature_loss.py quirk Q5 — so in training this is one tiny launch per optimizer step)."""
     from . import ops
     # the kernel and the GEMM descriptor tables are built for the model width 256 (the reference's InfoNCELoss(256, ...)); anything else would read out of bounds.
     # Writers that change W behind torch's version counter (W.data[...] = ..., raw kernels) other than FlatAdamW must call ops.bump_weight_generation().
@@ -22,11 +24,11 @@ def _wsym(W):
         raise ValueError(f"InfoNCE W must be fp32 [256, 256] (got {W.dtype} {tuple(W.shape)})")
     key = (W.data_ptr(), W._version, ops._weight_generation, W.device)
     hit = _WSYM.get("w")
-    if hit is None or hit[0] != key:
+    if hit is None or hit[0]() is not W or hit[1] != key:
         out = torch.empty(256, 256, dtype=torch.float32, device=W.device)
         L.check(L.load().dreg_infonce_wsym(L.ptr(W.detach().contiguous()), L.ptr(out), 256, L.stream()), "dreg_infonce_wsym")
-        _WSYM["w"] = hit = (key, out)
-    return hit[1]
+        _WSYM["w"] = hit = (weakref.ref(W), key, out)
+    return hit[2]
 
 
 def _gemm_tables(tab, dev):
