@@ -1,10 +1,27 @@
-// Device code shared by the ray marchers over a NeRF block's occupancy grid (gfx950, wave64): the surface-visibility labels of
-// visibility.hip and the volume renderer of render.hip.  Both march one ray per lane, 64 rays per wave, through the same three steps:
+// What the ray marchers over a NeRF block's occupancy grid share (gfx950, wave64): the surface-visibility labels (visibility.hip), the volume
+// renderer (render.hip), its training backward (render_train.hip) and the two-block renderer (render_pair.hip).  All march one ray per lane,
+// 64 rays per wave.  Stated here once:
+//   * MarchBlock, march_fill_block, march_pass_bound — one block as a marcher reads it, and the ONE host function that validates and fills it
+//                       from an entry point's arguments (nulls, grid dimensions, step, the 32,768-bit coarse rule, the scene diagonal and n_max);
+//   * march_load_coarse, march_grid — the device set-up: coarse bits into LDS, the MarchGrid of a block;
+//   * march_take      — one refill round: lanes without a ray take consecutive rays from a queue (MarchQueue) or a wave's own chunk (MarchChunk);
 //   * march_advance   — the lane's next lattice sample t_mid = t_min + (n + 1/2) dt that lies in an occupied cell of the binary grid
 //                       (nerfacc 0.3.5's marching rule; empty cells, and with the coarse bits empty 4^3 blocks, are skipped to their exit);
 //   * march_density   — the density of the wave's 64 samples: hash-grid gather per lane, then the 32 -> 64 -> 16 MLP on fp16 MFMA
 //                       through LDS (both stated in csrc/ngp_field.h, which the dense query of ngp.hip calls as well);
-//   * the caller's own use of sigma (labels there, compositing here).
+//   * march_sigma, march_composite, march_color_row — a renderer's sample step: sigma -> alpha -> survival -> T_all -> w, T_s with
+//                       sigma_eff = omega sigma (omega = 1 outside render_pair.hip), then the colour net's input row of a survivor;
+//   * march_load_color_w, march_color, march_sigmoid_f16, render_ray_interval, render_sh4_f16 — the colour net and a renderer's ray set-up.
+// The bit-for-bit contracts between the kernels (pair == render, train(jitter 0) == render, persistent == lock-step labels) rest on these being
+// the same code.  Deliberately left apart:
+//   * surface_visibility_kernel keeps its own advance loop: it is the reference the persistent form is tested against;
+//   * vis_ray_setup keeps its own slab test: it has no parallel-axis case and no near / far, so its result on d[k] == 0 differs from
+//     render_ray_interval's;
+//   * visibility's sample update (best, stop_T) is another rule than march_composite and stays in visibility.hip;
+//   * render_pair.hip's block loop stays one non-unrolled body that reads the block from the kernel-argument segment (its header says why);
+//   * two kernels at the edge of their budgets keep one helper's body written out, and say so where they do: ngp_render_bwd_kernel fills its
+//     MarchGrid itself (through march_grid it reserved more scratch), ngp_render_kernel its sample step (through march_composite / march_color_row
+//     its training forward measured slower).  The arithmetic is the helpers'; the bit-for-bit tests between the kernels hold it there.
 #pragma once
 #include "ngp_field.h"   // NgpLevels, NGP_XRS / NGP_HRS, wave_sync, the level gather and the density MLP
 
@@ -15,6 +32,105 @@ struct MarchGrid {
     float roi[6], roi_ext[3];
     int rdim[3], ry, rz, cy, cz;
 };
+
+// One block as a marcher reads it.  The kernel-argument structs of the four marchers begin with one; march_fill_block writes every field.
+struct MarchBlock {
+    const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
+    const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]; null where the marcher has none
+    NgpLevels lv;
+    const uint8_t* binary;                     // [rx,ry,rz] occupancy over the roi aabb
+    const uint32_t* coarse;                    // optional: one bit per 4^3 block of `binary` (dreg_occupancy_coarse_bits), <= 32,768 bits; null = none
+    int rx, ry, rz, cx, cy, cz;                // c* = ceil(r* / 4)
+    float roi[6], scene[6], model[6];
+    float near, far, dt, alpha_thre;
+    int n_max;                                 // samples per ray <= ceil(scene diagonal / dt) + 2; 0 where no scene interval is marched
+};
+
+// Validate and fill one block from an entry point's own arguments: DREG_OK, or DREG_EINVAL with nothing launched.  color: the marcher runs the
+// colour net (cw1..cw3 required).  scene_interval: rays are marched through the scene aabb, so a degenerate aabb or a step too small to march
+// it (diagonal / dt > 1e8) is rejected and n_max is set (<= 1e8 + 2: conversions of per-ray bounds to int cannot overflow).
+static inline int march_fill_block(MarchBlock& b, const uint8_t* binary, int rx, int ry, int rz, const uint32_t* coarse_bits,
+                                   const void* table, const void* w1, const void* w2, bool color, const void* cw1, const void* cw2, const void* cw3,
+                                   const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                                   const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                                   float render_step_size, float alpha_thre, bool scene_interval)
+{
+    if (!binary || !table || !w1 || !w2 || (color && (!cw1 || !cw2 || !cw3)) || !offset || !size || !res || !scale || !hashed ||
+        !roi_aabb || !scene_aabb || !model_aabb)
+        return DREG_EINVAL;
+    if (rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
+    b.table = (const _Float16*)table; b.w1 = (const _Float16*)w1; b.w2 = (const _Float16*)w2;
+    b.cw1 = (const _Float16*)cw1; b.cw2 = (const _Float16*)cw2; b.cw3 = (const _Float16*)cw3;
+    ngp_fill_levels(b.lv, offset, size, res, scale, hashed);
+    for (int k = 0; k < 6; ++k) { b.roi[k] = roi_aabb[k]; b.scene[k] = scene_aabb[k]; b.model[k] = model_aabb[k]; }
+    b.binary = binary; b.rx = rx; b.ry = ry; b.rz = rz;
+    b.cx = (rx + 3) / 4; b.cy = (ry + 3) / 4; b.cz = (rz + 3) / 4;
+    b.coarse = ((long)b.cx * b.cy * b.cz <= 32768) ? coarse_bits : nullptr;      // (the kernels keep a block's bits in 4 KB of LDS)
+    b.near = near_plane; b.far = far_plane; b.dt = render_step_size; b.alpha_thre = alpha_thre;
+    b.n_max = 0;
+    if (scene_interval) {
+        double diag = 0.0;
+        for (int k = 0; k < 3; ++k) { const double e = (double)scene_aabb[3 + k] - (double)scene_aabb[k]; diag += e * e; }
+        diag = __builtin_sqrt(diag);
+        if (!(diag >= 0.0) || diag / render_step_size > 1e8) return DREG_EINVAL;
+        b.n_max = (int)__builtin_ceil(diag / render_step_size) + 2;
+    }
+    return DREG_OK;
+}
+
+// Passes of a persistent march loop per wave, a safety net: every pass takes a ray, a sample or a lattice step.
+static inline long march_pass_bound(long rays, double steps_per_ray)
+{
+    const double passes = (double)rays * steps_per_ray + 64.0;
+    return passes > 1e15 ? (long)1e15 : (long)passes;
+}
+
+// The block's coarse bits into the one-wave workgroup's LDS (the caller's __syncthreads follows), and the grid a march of the block walks.
+__device__ __forceinline__ void march_load_coarse(uint32_t* sCoarse, const MarchBlock& b, int lane)
+{
+    if (b.coarse != nullptr) {
+        const int nw = (b.cx * b.cy * b.cz + 31) / 32;
+        for (int i = lane; i < nw; i += 64) sCoarse[i] = b.coarse[i];
+    }
+}
+__device__ __forceinline__ void march_grid(MarchGrid& g, const MarchBlock& b, const uint32_t* sCoarse)
+{
+    g.binary = b.binary; g.sCoarse = b.coarse != nullptr ? sCoarse : nullptr;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.roi[k] = b.roi[k]; g.roi[3 + k] = b.roi[3 + k]; g.roi_ext[k] = b.roi[3 + k] - b.roi[k]; }
+    g.rdim[0] = b.rx; g.rdim[1] = b.ry; g.rdim[2] = b.rz; g.ry = b.ry; g.rz = b.rz; g.cy = b.cy; g.cz = b.cz;
+}
+
+// Where a refill round's rays come from: the first of popc(mask) consecutive ray indices, the same value in every lane.
+struct MarchQueue {          // a counter in device memory shared by all waves: one atomic per wave and round
+    unsigned long long* counter;
+    __device__ __forceinline__ unsigned long long operator()(unsigned long long mask, int lane)
+    {
+        unsigned long long base = 0;
+        const int leader = __ffsll((long long)mask) - 1;
+        if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+        return __shfl(base, leader, 64);
+    }
+};
+struct MarchChunk {          // a run of rays that is this wave's own: no atomics
+    long next;
+    __device__ __forceinline__ unsigned long long operator()(unsigned long long mask, int)
+    {
+        const long base = next;
+        next += (long)__popcll(mask);
+        return (unsigned long long)base;
+    }
+};
+// One refill round: the lanes with `need` take consecutive rays from src in lane order.  False: no lane needs one, nothing was taken.  True:
+// ray = this lane's index where need is set (the caller compares it with its ray count and sets the ray up: that part is each kernel's own).
+template <class Src>
+__device__ __forceinline__ bool march_take(Src& src, bool need, int lane, unsigned long long& ray)
+{
+    const unsigned long long mask = __ballot(need);
+    if (!mask) return false;
+    ray = src(mask, lane) + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+    return true;
+}
 
 // Rounding allowance, in position, of a lattice sample's distance to a cell face on one axis.  A sample's fp32 coordinate
 // x = fl(o + fl(t d)) with t = fl(t_min + fl((n + 1/2) dt)) is within 2^-24 (|o| + 6 |t d|) of the exact line, and its cell index
@@ -157,6 +273,44 @@ __device__ __forceinline__ void render_sh4_f16(const float (&d)[3], uint32_t (&s
         const f16x2_t p = {(_Float16)sh[2 * j], (_Float16)sh[2 * j + 1]};
         sh2[j] = __builtin_bit_cast(uint32_t, p);
     }
+}
+
+// Density of a sample from the logit march_density left in sOut: sigma = exp(h0 - 1), 0 outside the model aabb.
+__device__ __forceinline__ float march_sigma(bool inside_m, float h0) { return inside_m ? __expf(h0 - 1.f) : 0.f; }
+
+// A renderer's step for one marched sample of a ray, in ray order: alpha = 1 - exp(-omega sigma dt); the sample SURVIVES iff T_all >= eps and
+// (alpha_thre == 0 or alpha >= alpha_thre); T_all runs over all marched samples, T_s and the weight w = alpha T_s over the survivors only.
+// omega: the overlap weight of render_pair.hip; the one-block renderers pass 1.f (1.f * sigma is sigma).
+__device__ __forceinline__ bool march_composite(float sigma, float omega, float dt, float eps, float alpha_thre, float& T_all, float& T_s, float& w)
+{
+    const float sigma_eff = omega * sigma;
+    const float alpha = 1.f - __expf(-sigma_eff * dt);
+    const bool surv = T_all >= eps && (alpha_thre <= 0.f || alpha >= alpha_thre);
+    T_all *= (1.f - alpha);
+    if (surv) {
+        w = alpha * T_s;
+        T_s *= (1.f - alpha);
+    }
+    return surv;
+}
+
+// A survivor's input row of the colour net: fp16 SH4(d) in columns 0..15 and the constant 1 in column 31, around the 15 features march_density left.
+__device__ __forceinline__ void march_color_row(char* sX, int lane, const uint32_t (&sh2)[8])
+{
+    uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
+    reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
+}
+
+// The colour net's first / last layer as this lane's MFMA operands (march_color's cw1f / cw3f).
+__device__ __forceinline__ void march_load_color_w(f16x8_t (&cw1f)[4], f16x8_t (&cw3f)[2], const _Float16* cw1, const _Float16* cw3, int lane)
+{
+    const int fr = lane & 15, kg = lane >> 4;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(cw1 + (cb * 16 + fr) * 32 + kg * 8);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(cw3 + fr * 64 + kb * 32 + kg * 8);
 }
 
 // The colour net of the wave's 64 rows of sX (fp16 SH4(d) | 15 features | 1) -> relu 64 (sH1) -> relu 64 (sH2) -> 3 (sO[row*4 + ch], fp32 pre-

@@ -22,22 +22,14 @@
 #include "march.h"
 #include "../../include/dreg_nerf.h"   // signature check of the entry point defined here
 
-struct RenderArgs {
+struct RenderArgs : MarchBlock {       // the block (march.h; every ray's ceil((t_max - t_min) / dt) + 1 is below its n_max), then the launch's own
     const float* origins;       // [N,3]
     const float* dirs;          // [N,3] unit viewing directions
     const float* jitter;        // [N] per-ray u in [0,1) of stratified marching (dreg_ngp_render_train); null = 0 (dreg_ngp_render)
     long n_rays;
-    const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
-    const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]
-    NgpLevels lv;
-    const uint8_t* binary;
-    const uint32_t* coarse;     // optional coarse bits (dreg_occupancy_coarse_bits), <= 32,768 bits; null = none
-    int rx, ry, rz, cx, cy, cz;
-    float roi[6], scene[6], model[6];
-    float near, far, dt, alpha_thre, eps;
+    float eps;
     float bkgd[3];
-    int n_max;                  // samples per ray <= ceil(aabb diagonal / dt) + 1 (every ray's ceil((t_max - t_min) / dt) + 1 is below it)
-    long pass_bound;            // passes of the march loop per wave: n_rays * (n_max + 2) + 64 (a safety net: every pass takes a ray or a step)
+    long pass_bound;            // passes of the march loop per wave: n_rays * (n_max + 2) + 64 (march_pass_bound)
     float *rgb, *opacity, *depth;
     unsigned long long* n_samples;
     unsigned long long* queue;
@@ -61,25 +53,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
     __shared__ uint32_t sCoarse[1024];
     const int lane = threadIdx.x;
-    const int fr = lane & 15, kg = lane >> 4;
-    const bool use_coarse = a.coarse != nullptr;
-    if (use_coarse) {
-        const int nw = (a.cx * a.cy * a.cz + 31) / 32;
-        for (int i = lane; i < nw; i += 64) sCoarse[i] = a.coarse[i];
-    }
+    march_load_coarse(sCoarse, a, lane);
     __syncthreads();
     MarchGrid g;
-    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
-    g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
+    march_grid(g, a, sCoarse);
     NgpDensityW dw;
     ngp_load_density_w(dw, a.w1, a.w2, lane);
     f16x8_t cw1f[4], cw3f[2];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(a.cw3 + fr * 64 + kb * 32 + kg * 8);
+    march_load_color_w(cw1f, cw3f, a.cw1, a.cw3, lane);
+    MarchQueue queue = {a.queue};
 
     // per-lane ray state
     bool active = false, exhausted = false;
@@ -97,14 +79,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         // ---- refill: lanes without a ray take the next ones from the queue; rays that miss the aabb are written at once
         for (int tries = 0; tries < 1024; ++tries) {
             const bool need = !active && !exhausted;
-            const unsigned long long mask = __ballot(need);
-            if (!mask) break;
-            unsigned long long base = 0;
-            const int leader = __ffsll((long long)mask) - 1;
-            if (lane == leader) base = atomicAdd(a.queue, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader, 64);
+            unsigned long long r = 0;
+            if (!march_take(queue, need, lane, r)) break;
             if (need) {
-                const unsigned long long r = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
                 if (r >= (unsigned long long)a.n_rays) exhausted = true;
                 else {
                     ray = (long)r;
@@ -139,6 +116,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         bool surv = false;
         float w = 0.f;
         if (have) {
+            // march_composite and march_color_row with omega = 1, kept local: through the helpers the training forward of this kernel measured
+            // ~2 % slower (the arithmetic is theirs operation for operation: tests/test_hip_render_pair.py holds the two kernels equal bit for bit)
             const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
             const float alpha = 1.f - __expf(-sigma * a.dt);
             surv = T_all >= a.eps && (a.alpha_thre <= 0.f || alpha >= a.alpha_thre);
@@ -185,29 +164,17 @@ static int render_launch(const float* origins, const float* viewdirs, const floa
                          float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
                          float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue, void* stream)
 {
-    if (n_rays < 0 || rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
+    if (n_rays < 0) return DREG_EINVAL;
     if (n_rays == 0) return DREG_OK;
-    if (!origins || !viewdirs || !binary || !table || !w1 || !w2 || !cw1 || !cw2 || !cw3 || !offset || !size || !res || !scale || !hashed ||
-        !roi_aabb || !scene_aabb || !model_aabb || !bkgd || !rgb || !opacity || !depth || !n_samples || !queue)
-        return DREG_EINVAL;
+    if (!origins || !viewdirs || !bkgd || !rgb || !opacity || !depth || !n_samples || !queue) return DREG_EINVAL;
     RenderArgs a;
+    if (march_fill_block(a, binary, rx, ry, rz, coarse_bits, table, w1, w2, true, cw1, cw2, cw3, offset, size, res, scale, hashed,
+                         roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, true) != DREG_OK)
+        return DREG_EINVAL;
     a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
-    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
-    a.cw1 = (const _Float16*)cw1; a.cw2 = (const _Float16*)cw2; a.cw3 = (const _Float16*)cw3;
-    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
-    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
+    a.eps = early_stop_eps;
     for (int k = 0; k < 3; ++k) a.bkgd[k] = bkgd[k];
-    a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;
-    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
-    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;      // (the kernel keeps the bits in 4 KB of LDS)
-    a.near = near_plane; a.far = far_plane; a.dt = render_step_size; a.alpha_thre = alpha_thre; a.eps = early_stop_eps;
-    double diag = 0.0;
-    for (int k = 0; k < 3; ++k) { const double e = (double)scene_aabb[3 + k] - (double)scene_aabb[k]; diag += e * e; }
-    diag = __builtin_sqrt(diag);
-    if (!(diag >= 0.0) || diag / render_step_size > 1e8) return DREG_EINVAL;        // (a degenerate aabb or a step too small to march)
-    a.n_max = (int)__builtin_ceil(diag / render_step_size) + 2;
-    const double passes = (double)n_rays * (double)(a.n_max + 2) + 64.0;
-    a.pass_bound = passes > 1e15 ? (long)1e15 : (long)passes;
+    a.pass_bound = march_pass_bound(n_rays, (double)(a.n_max + 2));
     a.rgb = rgb; a.opacity = opacity; a.depth = depth; a.n_samples = n_samples; a.queue = (unsigned long long*)queue;
     long waves = (n_rays + 63) / 64;
     if (waves > g_render_waves) waves = g_render_waves;

@@ -37,19 +37,10 @@
 #include "march.h"
 #include "../../include/dreg_nerf.h"   // signature check of the entry point defined here
 
-struct PairBlock {
+struct PairBlock : MarchBlock {
     const float* origins;       // [N,3] in this block's frame
     const float* dirs;          // [N,3] unit viewing directions in this block's frame
-    const _Float16 *table, *w1, *w2;           // density net (fp16 inference copies of mlp_base.params)
-    const _Float16 *cw1, *cw2, *cw3;           // colour net (color_mlp.params): [64][32], [64][64], [16][64]
-    NgpLevels lv;
-    const uint8_t* binary;
-    const uint32_t* coarse;     // optional coarse bits, <= 32,768 bits; null = none
-    int rx, ry, rz, cx, cy, cz;
-    float roi[6], scene[6], model[6];
-    float near, far, dt, alpha_thre;
     float center[3];            // centroid of the block's cameras, in the block's frame
-    int n_max;                  // samples per ray <= ceil(aabb diagonal / dt) + 2
 };
 
 struct PairArgs {
@@ -72,14 +63,6 @@ struct PairCursor {
     int n, n_lim;
     bool act, pend;
 };
-
-__device__ __forceinline__ void pair_grid(MarchGrid& g, const PairBlock& b, const uint32_t* sCoarse)
-{
-    g.binary = b.binary; g.sCoarse = b.coarse != nullptr ? sCoarse : nullptr;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.roi[k] = b.roi[k]; g.roi[3 + k] = b.roi[3 + k]; g.roi_ext[k] = b.roi[3 + k] - b.roi[k]; }
-    g.rdim[0] = b.rx; g.rdim[1] = b.ry; g.rdim[2] = b.rz; g.ry = b.ry; g.rz = b.rz; g.cy = b.cy; g.cz = b.cz;
-}
 
 __device__ __forceinline__ void pair_take_ray(const PairBlock& b, PairCursor& c, long ray)
 {
@@ -139,7 +122,6 @@ __device__ __forceinline__ void pair_phase(const PairArgs& a, const PairBlock& b
                                            float tm, float omega, char* sX, char* sH, float* sOut, float* sO, PairAccum& r, int lane)
 {
     if (!__any(have)) return;
-    const int fr = lane & 15, kg = lane >> 4;
     bool surv = false;
     float w = 0.f;
     {
@@ -147,29 +129,17 @@ __device__ __forceinline__ void pair_phase(const PairArgs& a, const PairBlock& b
         ngp_load_density_w(dw, b.w1, b.w2, lane);
         const bool inside_m = march_density<true>(have, x, b.model, b.lv, b.table, dw, sX, sH, sOut, lane);
         if (have) {
-            const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
-            const float sigma_eff = omega * sigma;
-            const float alpha = 1.f - __expf(-sigma_eff * b.dt);
-            surv = r.T_all >= a.eps && (b.alpha_thre <= 0.f || alpha >= b.alpha_thre);
-            r.T_all *= (1.f - alpha);
+            surv = march_composite(march_sigma(inside_m, sOut[lane]), omega, b.dt, a.eps, b.alpha_thre, r.T_all, r.T_s, w);
             if (surv) {
-                w = alpha * r.T_s;
-                r.T_s *= (1.f - alpha);
                 uint32_t sh2[8];
                 render_sh4_f16(dir, sh2);
-                uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
-                reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
+                march_color_row(sX, lane, sh2);
             }
         }
     }
     if (__any(surv)) {
         f16x8_t cw1f[4], cw3f[2];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(b.cw1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(b.cw3 + fr * 64 + kb * 32 + kg * 8);
+        march_load_color_w(cw1f, cw3f, b.cw1, b.cw3, lane);
         march_color(sX, sH, sH, sO, cw1f, b.cw2, cw3f, lane);
         if (surv) {
             const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
@@ -193,17 +163,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
     __shared__ uint32_t sCoarse[2][1024];
     const int lane = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        if (a.b[q].coarse != nullptr) {
-            const int nw = (a.b[q].cx * a.b[q].cy * a.b[q].cz + 31) / 32;
-            for (int i = lane; i < nw; i += 64) sCoarse[q][i] = a.b[q].coarse[i];
-        }
-    }
+    march_load_coarse(sCoarse[0], a.b[0], lane);
+    march_load_coarse(sCoarse[1], a.b[1], lane);
     __syncthreads();
     MarchGrid g0, g1;
-    pair_grid(g0, a.b[0], sCoarse[0]);
-    pair_grid(g1, a.b[1], sCoarse[1]);
+    march_grid(g0, a.b[0], sCoarse[0]);
+    march_grid(g1, a.b[1], sCoarse[1]);
+    MarchQueue queue = {a.queue};
 
     // per-lane ray state
     bool live = false, exhausted = false;
@@ -221,14 +187,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         // ---- refill: lanes without a ray take the next ones from the queue; rays that miss both aabbs are written at once
         for (int tries = 0; tries < 1024; ++tries) {
             const bool need = !live && !exhausted;
-            const unsigned long long mask = __ballot(need);
-            if (!mask) break;
-            unsigned long long base = 0;
-            const int leader = __ffsll((long long)mask) - 1;
-            if (lane == leader) base = atomicAdd(a.queue, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader, 64);
+            unsigned long long q = 0;
+            if (!march_take(queue, need, lane, q)) break;
             if (need) {
-                const unsigned long long q = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
                 if (q >= (unsigned long long)a.n_rays) exhausted = true;
                 else {
                     ray = (long)q;
@@ -307,43 +268,26 @@ struct PairBlockHost {
     const float* center;
 };
 
-static bool pair_dims_ok(const PairBlockHost& h) { return h.rx > 0 && h.ry > 0 && h.rz > 0 && h.render_step_size > 0.f; }
-
-static bool pair_fill_block(PairBlock& b, const PairBlockHost& h)
+static int pair_fill_block(PairBlock& b, const PairBlockHost& h)
 {
-    if (!h.origins || !h.viewdirs || !h.binary || !h.table || !h.w1 || !h.w2 || !h.cw1 || !h.cw2 || !h.cw3 || !h.offset || !h.size || !h.res ||
-        !h.scale || !h.hashed || !h.roi_aabb || !h.scene_aabb || !h.model_aabb || !h.center)
-        return false;
+    if (!h.origins || !h.viewdirs || !h.center) return DREG_EINVAL;
     b.origins = h.origins; b.dirs = h.viewdirs;
-    b.table = (const _Float16*)h.table; b.w1 = (const _Float16*)h.w1; b.w2 = (const _Float16*)h.w2;
-    b.cw1 = (const _Float16*)h.cw1; b.cw2 = (const _Float16*)h.cw2; b.cw3 = (const _Float16*)h.cw3;
-    ngp_fill_levels(b.lv, h.offset, h.size, h.res, h.scale, h.hashed);
-    for (int k = 0; k < 6; ++k) { b.roi[k] = h.roi_aabb[k]; b.scene[k] = h.scene_aabb[k]; b.model[k] = h.model_aabb[k]; }
     for (int k = 0; k < 3; ++k) b.center[k] = h.center[k];
-    b.binary = h.binary; b.rx = h.rx; b.ry = h.ry; b.rz = h.rz;
-    b.cx = (h.rx + 3) / 4; b.cy = (h.ry + 3) / 4; b.cz = (h.rz + 3) / 4;
-    b.coarse = ((long)b.cx * b.cy * b.cz <= 32768) ? h.coarse_bits : nullptr;      // (the kernel keeps each block's bits in 4 KB of LDS)
-    b.near = h.near_plane; b.far = h.far_plane; b.dt = h.render_step_size; b.alpha_thre = h.alpha_thre;
-    double diag = 0.0;
-    for (int k = 0; k < 3; ++k) { const double e = (double)h.scene_aabb[3 + k] - (double)h.scene_aabb[k]; diag += e * e; }
-    diag = __builtin_sqrt(diag);
-    if (!(diag >= 0.0) || diag / h.render_step_size > 1e8) return false;          // (a degenerate aabb or a step too small to march)
-    b.n_max = (int)__builtin_ceil(diag / h.render_step_size) + 2;
-    return true;
+    return march_fill_block(b, h.binary, h.rx, h.ry, h.rz, h.coarse_bits, h.table, h.w1, h.w2, true, h.cw1, h.cw2, h.cw3, h.offset, h.size, h.res, h.scale,
+                            h.hashed, h.roi_aabb, h.scene_aabb, h.model_aabb, h.near_plane, h.far_plane, h.render_step_size, h.alpha_thre, true);
 }
 
 static int render_pair_launch(const PairBlockHost& src, const PairBlockHost& tgt, long n_rays, float power, float early_stop_eps, const float* bkgd,
                               float* rgb, float* opacity, float* depth, float* weight_src, unsigned long long* n_samples, void* queue, void* stream)
 {
-    if (n_rays < 0 || !(power >= 0.f) || !(power <= 1e4f) || !pair_dims_ok(src) || !pair_dims_ok(tgt)) return DREG_EINVAL;
+    if (n_rays < 0 || !(power >= 0.f) || !(power <= 1e4f)) return DREG_EINVAL;
     if (n_rays == 0) return DREG_OK;
     if (!bkgd || !rgb || !opacity || !depth || !weight_src || !n_samples || !queue) return DREG_EINVAL;
     PairArgs a;
-    if (!pair_fill_block(a.b[0], src) || !pair_fill_block(a.b[1], tgt)) return DREG_EINVAL;
+    if (pair_fill_block(a.b[0], src) != DREG_OK || pair_fill_block(a.b[1], tgt) != DREG_OK) return DREG_EINVAL;
     a.n_rays = n_rays; a.half_power = 0.5f * power; a.eps = early_stop_eps;
     for (int k = 0; k < 3; ++k) a.bkgd[k] = bkgd[k];
-    const double passes = (double)n_rays * ((double)a.b[0].n_max + (double)a.b[1].n_max + 2.0) + 64.0;
-    a.pass_bound = passes > 1e15 ? (long)1e15 : (long)passes;
+    a.pass_bound = march_pass_bound(n_rays, (double)a.b[0].n_max + (double)a.b[1].n_max + 2.0);
     a.rgb = rgb; a.opacity = opacity; a.depth = depth; a.weight_src = weight_src; a.n_samples = n_samples; a.queue = (unsigned long long*)queue;
     long waves = (n_rays + 63) / 64;
     if (waves > g_render_pair_waves) waves = g_render_pair_waves;

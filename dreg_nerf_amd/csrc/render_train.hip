@@ -27,19 +27,12 @@ constexpr int BWD_OFF_D1 = 0, BWD_OFF_D2 = 2048, BWD_OFF_C1 = 3072, BWD_OFF_C2 =
 constexpr long BWD_MAX_CHUNKS = 2048;
 constexpr int BWD_AS = 68;             // row stride (floats) of the wave's fp32 delta tile sA [64 samples][<= 64]
 
-struct RenderBwdArgs {
+struct RenderBwdArgs : MarchBlock {    // the forward's block (march.h), then the launch's own
     const float *origins, *dirs, *jitter;
     long n_rays;
-    const _Float16 *table, *w1, *w2, *cw1, *cw2, *cw3;
     const float* wf;                   // fp32 copies of the five weight matrices, slab layout
-    NgpLevels lv;
-    const uint8_t* binary;
-    const uint32_t* coarse;
-    int rx, ry, rz, cx, cy, cz;
-    float roi[6], scene[6], model[6];
-    float near, far, dt, alpha_thre, eps;
-    int n_max;
-    long pass_bound;                   // passes per chunk: chunk_rays * (n_max + 2) + 64
+    float eps;
+    long pass_bound;                   // passes per chunk: chunk_rays * (n_max + 2) + 64 (march_pass_bound)
     const float *rgb, *grad_rgb;       // forward rgb (with background) and dL/drgb, fp32 [N,3]
     float* grad_table;                 // fp32 [entries][2], accumulated with atomics
     float* slabs;                      // fp32 [n_chunks][BWD_SLAB], zeroed by the entry point
@@ -89,25 +82,17 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
     __shared__ uint32_t sCoarse[1024];
     const int lane = threadIdx.x;
-    const int fr = lane & 15, kg = lane >> 4;
-    const bool use_coarse = a.coarse != nullptr;
-    if (use_coarse) {
-        const int nw = (a.cx * a.cy * a.cz + 31) / 32;
-        for (int i = lane; i < nw; i += 64) sCoarse[i] = a.coarse[i];
-    }
+    march_load_coarse(sCoarse, a, lane);
     __syncthreads();
-    MarchGrid g;
-    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
+    MarchGrid g;               // march_grid's body, kept local: through the helper this kernel, at its register limit, reserved 16 more bytes of scratch per lane
+    g.binary = a.binary; g.sCoarse = a.coarse != nullptr ? sCoarse : nullptr;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
     g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
     NgpDensityW dw;
     ngp_load_density_w(dw, a.w1, a.w2, lane);
     f16x8_t cw1f[4], cw3f[2];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) cw1f[cb] = *reinterpret_cast<const f16x8_t*>(a.cw1 + (cb * 16 + fr) * 32 + kg * 8);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) cw3f[kb] = *reinterpret_cast<const f16x8_t*>(a.cw3 + fr * 64 + kb * 32 + kg * 8);
+    march_load_color_w(cw1f, cw3f, a.cw1, a.cw3, lane);
     const float* wd1 = a.wf + BWD_OFF_D1;
     const float* wd2 = a.wf + BWD_OFF_D2;
     const float* wc1 = a.wf + BWD_OFF_C1;
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
         const long r0 = (long)chunk * a.chunk_rays;
         const long r1 = min(a.n_rays, r0 + a.chunk_rays);
         float* slab = a.slabs + (size_t)chunk * BWD_SLAB;
-        long next = r0;
+        MarchChunk own = {r0};
         bool active = false, exhausted = false;
         long ray = 0;
         int n = 0, n_lim = 0;
@@ -136,13 +121,12 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
             // ---- refill from the chunk's rays in lane order (no atomics: the chunk is this wave's)
             for (int tries = 0; tries < 1024; ++tries) {
                 const bool need = !active && !exhausted;
-                const unsigned long long mask = __ballot(need);
-                if (!mask) break;
+                unsigned long long r = 0;
+                if (!march_take(own, need, lane, r)) break;
                 if (need) {
-                    const long r = next + (long)__popcll(mask & ((1ull << lane) - 1ull));
-                    if (r >= r1) exhausted = true;
+                    if ((long)r >= r1) exhausted = true;
                     else {
-                        ray = r;
+                        ray = (long)r;
 #pragma unroll
                         for (int k = 0; k < 3; ++k) { o[k] = a.origins[ray * 3 + k]; d[k] = a.dirs[ray * 3 + k]; }
                         const bool hit = render_ray_interval(o, d, a.scene, a.near, a.far, tmin, tmax);
@@ -156,7 +140,6 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                         }
                     }
                 }
-                next += (long)__popcll(mask);
             }
             if (!__any(active)) {
                 if (__all(exhausted)) break;
@@ -172,19 +155,9 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
             float w = 0.f, h0 = 0.f;
             if (have) {
                 h0 = sOut[lane];
-                const float sigma = inside_m ? __expf(h0 - 1.f) : 0.f;
-                const float alpha = 1.f - __expf(-sigma * a.dt);
-                surv = T_all >= a.eps && (a.alpha_thre <= 0.f || alpha >= a.alpha_thre);
-                T_all *= (1.f - alpha);
+                surv = march_composite(march_sigma(inside_m, h0), 1.f, a.dt, a.eps, a.alpha_thre, T_all, T_s, w);      // (a survivor's T_s is now T_{k+1})
                 ++n;
-                if (surv) {
-                    w = alpha * T_s;
-                    T_s *= (1.f - alpha);                                 // = T_{k+1}
-                    uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
-                    reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
-                }
+                if (surv) march_color_row(sX, lane, sh2);
             }
             if (__any(surv)) {
                 sLive[lane] = surv ? 1.f : 0.f;
@@ -367,11 +340,9 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
                         float render_step_size, float alpha_thre, float early_stop_eps,
                         const float* rgb, const float* grad_rgb, float* grad_base, float* grad_color, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (n_rays < 0 || rx <= 0 || ry <= 0 || rz <= 0 || !(render_step_size > 0.f)) return DREG_EINVAL;
+    if (n_rays < 0) return DREG_EINVAL;
     if (n_rays == 0) return DREG_OK;
-    if (!origins || !viewdirs || !jitter || !binary || !base16 || !color16 || !offset || !size || !res || !scale || !hashed || !roi_aabb || !scene_aabb ||
-        !model_aabb || !rgb || !grad_rgb || !grad_base || !grad_color || !workspace)
-        return DREG_EINVAL;
+    if (!origins || !viewdirs || !jitter || !base16 || !color16 || !rgb || !grad_rgb || !grad_base || !grad_color || !workspace) return DREG_EINVAL;
     RenderBwdArgs a;
     size_t slab_off, queue_off, total;
     if (bwd_layout(n_rays, &a.chunk_rays, &a.n_chunks, &slab_off, &queue_off, &total) != DREG_OK || workspace_bytes < total) return DREG_EINVAL;
@@ -379,22 +350,12 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
     a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
     const _Float16* b16 = (const _Float16*)base16;
     const _Float16* c16 = (const _Float16*)color16;
-    a.w1 = b16; a.w2 = b16 + 2048; a.table = b16 + 3072;
-    a.cw1 = c16; a.cw2 = c16 + 2048; a.cw3 = c16 + 6144;
+    if (march_fill_block(a, binary, rx, ry, rz, coarse_bits, b16 + 3072, b16, b16 + 2048, true, c16, c16 + 2048, c16 + 6144, offset, size, res, scale, hashed,
+                         roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, true) != DREG_OK)
+        return DREG_EINVAL;
     a.wf = (const float*)ws;
-    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
-    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
-    a.binary = binary; a.rx = rx; a.ry = ry; a.rz = rz;
-    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
-    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;
-    a.near = near_plane; a.far = far_plane; a.dt = render_step_size; a.alpha_thre = alpha_thre; a.eps = early_stop_eps;
-    double diag = 0.0;
-    for (int k = 0; k < 3; ++k) { const double e = (double)scene_aabb[3 + k] - (double)scene_aabb[k]; diag += e * e; }
-    diag = __builtin_sqrt(diag);
-    if (!(diag >= 0.0) || diag / render_step_size > 1e8) return DREG_EINVAL;
-    a.n_max = (int)__builtin_ceil(diag / render_step_size) + 2;
-    const double passes = (double)a.chunk_rays * (double)(a.n_max + 2) + 64.0;
-    a.pass_bound = passes > 1e15 ? (long)1e15 : (long)passes;
+    a.eps = early_stop_eps;
+    a.pass_bound = march_pass_bound(a.chunk_rays, (double)(a.n_max + 2));
     a.rgb = rgb; a.grad_rgb = grad_rgb;
     a.grad_table = grad_base + 3072;
     a.slabs = (float*)(ws + slab_off);

@@ -13,19 +13,13 @@
 // over cameras with one atomic per hit.  nerfacc 0.3.5 / tcnn are absent from the reference tree: parity unpinned.
 #include "march.h"      // the lattice advance and the density of a wave's samples, shared with render.hip (field: ngp_field.h)
 #include <cstring>
-struct VisArgs {
+struct VisArgs : MarchBlock {   // the block (march.h; no colour net, no near / far, no n_max), then the launch's own
     const float* cams;     // [Nc,3] camera centres
     const float* pts;      // [Np,3]
-    const uint8_t* binary; // [rx,ry,rz] occupancy
     int* label;            // [Np] OR over cameras
-    const _Float16 *table, *w1, *w2;
-    NgpLevels lv;
-    float roi[6], scene[6], model[6];
-    int rx, ry, rz, Nc, Np;
-    float dt, cut_off, early_eps, alpha_thre;
+    int Nc, Np;
+    float cut_off, early_eps;
     int max_steps;
-    const uint32_t* coarse;   // optional: one bit per 4^3 block of `binary` (dreg_occupancy_coarse_bits), <= 32,768 bits; null = none
-    int cx, cy, cz;           // its extents: ceil(r / 4)
     unsigned long long* queue;   // persistent forms: this block's ray counter (zeroed by the caller)
 };
 
@@ -144,18 +138,13 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
     // in coarse cells looked up here (~100 cycles) instead of fine cells looked up in global memory (a dependent load of 1-2 us each);
     // every pass of the loop below waits for its slowest lane, and a freshly queued ray's walk WAS that lane
     __shared__ uint32_t sCoarse[1024];
-    const bool use_coarse = a.coarse != nullptr;
-    if (use_coarse) {
-        const int nw = (a.cx * a.cy * a.cz + 31) / 32;
-        for (int i = lane; i < nw; i += 64) sCoarse[i] = a.coarse[i];
-    }
-    __syncthreads();
     const unsigned long long nrays = (unsigned long long)a.Nc * (unsigned long long)a.Np;
+    if (nrays == 0) return;                                       // (a block without rays: its descriptor holds no pointers, dreg_surface_visibility_fill_desc)
+    march_load_coarse(sCoarse, a, lane);
+    __syncthreads();
     MarchGrid g;
-    g.binary = a.binary; g.sCoarse = use_coarse ? sCoarse : nullptr;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.roi[k] = a.roi[k]; g.roi[3 + k] = a.roi[3 + k]; g.roi_ext[k] = a.roi[3 + k] - a.roi[k]; }
-    g.rdim[0] = a.rx; g.rdim[1] = a.ry; g.rdim[2] = a.rz; g.ry = a.ry; g.rz = a.rz; g.cy = a.cy; g.cz = a.cz;
+    march_grid(g, a, sCoarse);
+    MarchQueue rays = {queue};
     const float stop_T = fmaxf(a.cut_off, a.early_eps);
     NgpDensityW dw;
     ngp_load_density_w(dw, a.w1, a.w2, lane);
@@ -171,14 +160,9 @@ __device__ __forceinline__ void vis_march_queue(const VisArgs& a, unsigned long 
         // ---- refill: lanes without a ray take the next ones from the queue, skipping rays whose point is already labelled
         for (int tries = 0; tries < 1024; ++tries) {
             const bool need = !active && !exhausted;
-            const unsigned long long mask = __ballot(need);
-            if (!mask) break;
-            unsigned long long base = 0;
-            const int leader = __ffsll((long long)mask) - 1;
-            if (lane == leader) base = atomicAdd(queue, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader, 64);
+            unsigned long long ray = 0;
+            if (!march_take(rays, need, lane, ray)) break;
             if (need) {
-                const unsigned long long ray = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
                 if (ray >= nrays) exhausted = true;
                 else {
                     const int c = (int)(ray / (unsigned long long)a.Np);
@@ -260,21 +244,20 @@ int dreg_occupancy_coarse_bits(const uint8_t* binary, uint32_t* bits, int rx, in
     return DREG_OK;
 }
 
-static void vis_fill(VisArgs& a, const float* cams, const float* pts, const uint8_t* binary, int* label, const void* table, const void* w1, const void* w2,
-                     const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
-                     const float* roi_aabb, const float* scene_aabb, const float* model_aabb, int rx, int ry, int rz, int Nc, int Np,
-                     float render_step_size, float cut_off, float early_stop_eps, float alpha_thre, void* queue, const uint32_t* coarse_bits)
+// One block's descriptor from an entry point's arguments, validated as the renderers validate theirs (march_fill_block): DREG_EINVAL, with
+// nothing launched, for a null pointer, an empty grid or a step that is not > 0 (the persistent kernel would spin to its pass bound on dt <= 0).
+static int vis_fill(VisArgs& a, const float* cams, const float* pts, const uint8_t* binary, int* label, const void* table, const void* w1, const void* w2,
+                    const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                    const float* roi_aabb, const float* scene_aabb, const float* model_aabb, int rx, int ry, int rz, int Nc, int Np,
+                    float render_step_size, float cut_off, float early_stop_eps, float alpha_thre, void* queue, const uint32_t* coarse_bits)
 {
-    a.cams = cams; a.pts = pts; a.binary = binary; a.label = label;
-    a.table = (const _Float16*)table; a.w1 = (const _Float16*)w1; a.w2 = (const _Float16*)w2;
-    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
-    for (int k = 0; k < 6; ++k) { a.roi[k] = roi_aabb[k]; a.scene[k] = scene_aabb[k]; a.model[k] = model_aabb[k]; }
-    a.rx = rx; a.ry = ry; a.rz = rz; a.Nc = Nc; a.Np = Np;
-    a.dt = render_step_size; a.cut_off = cut_off; a.early_eps = early_stop_eps; a.alpha_thre = alpha_thre;
+    if (!cams || !pts || !label || Nc < 0 || Np < 0) return DREG_EINVAL;
+    a.cams = cams; a.pts = pts; a.label = label; a.Nc = Nc; a.Np = Np;
+    a.cut_off = cut_off; a.early_eps = early_stop_eps;
     a.max_steps = 1 << 16;
-    a.cx = (rx + 3) / 4; a.cy = (ry + 3) / 4; a.cz = (rz + 3) / 4;
-    a.coarse = ((long)a.cx * a.cy * a.cz <= 32768) ? coarse_bits : nullptr;      // (the kernel keeps the bits in 4 KB of LDS)
     a.queue = (unsigned long long*)queue;
+    return march_fill_block(a, binary, rx, ry, rz, coarse_bits, table, w1, w2, false, nullptr, nullptr, nullptr, offset, size, res, scale, hashed,
+                            roi_aabb, scene_aabb, model_aabb, -INFINITY, INFINITY, render_step_size, alpha_thre, false);
 }
 // label[p] = OR over cameras of (max_samples alpha*T >= cut_off) along the ray camera -> point p (must be zeroed by the caller).
 // table/w1/w2: fp16 inference copies of mlp_base.params; level arrays / aabbs are HOST pointers (16 entries / 6 floats).
@@ -287,8 +270,9 @@ int dreg_surface_visibility(const float* cams, const float* pts, const uint8_t* 
 {
     if ((long)Nc * Np == 0) return DREG_OK;
     VisArgs a;
-    vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
-             render_step_size, cut_off, early_stop_eps, alpha_thre, nullptr, nullptr);
+    if (vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
+                 render_step_size, cut_off, early_stop_eps, alpha_thre, nullptr, nullptr) != DREG_OK)
+        return DREG_EINVAL;
     const long nrays = (long)Nc * Np;
     hipLaunchKernelGGL(surface_visibility_kernel, dim3((unsigned)((nrays + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     DREG_LAUNCH_CHECK();
@@ -307,8 +291,10 @@ int dreg_surface_visibility_fill_desc(void* host_desc, const float* cams, const 
 {
     if (!host_desc || !queue) return DREG_EINVAL;
     VisArgs a;
-    vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
-             render_step_size, cut_off, early_stop_eps, alpha_thre, queue, coarse_bits);
+    if ((long)Nc * Np == 0) memset(&a, 0, sizeof(a));            // no rays: the kernel returns before it reads anything else of the descriptor
+    else if (vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
+                      render_step_size, cut_off, early_stop_eps, alpha_thre, queue, coarse_bits) != DREG_OK)
+        return DREG_EINVAL;
     memcpy(host_desc, &a, sizeof(a));
     return DREG_OK;
 }
@@ -353,8 +339,9 @@ int dreg_surface_visibility_queue(const float* cams, const float* pts, const uin
     if ((long)Nc * Np == 0) return DREG_OK;
     if (!queue) return DREG_EINVAL;
     VisArgs a;
-    vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
-             render_step_size, cut_off, early_stop_eps, alpha_thre, queue, coarse_bits);
+    if (vis_fill(a, cams, pts, binary, label, table, w1, w2, offset, size, res, scale, hashed, roi_aabb, scene_aabb, model_aabb, rx, ry, rz, Nc, Np,
+                 render_step_size, cut_off, early_stop_eps, alpha_thre, queue, coarse_bits) != DREG_OK)
+        return DREG_EINVAL;
     const long nrays = (long)Nc * Np;
     long waves = (nrays + 63) / 64;
     if (waves > g_vis_waves) waves = g_vis_waves;

@@ -400,6 +400,20 @@ def ptr(t):
     return t.data_ptr()
 
 
+def _floats(n, v):
+    return (c_float * n)(*[float(t) for t in (v.reshape(-1).tolist() if torch.is_tensor(v) else v)])
+
+
+def f6(v):
+    """An aabb (tensor or sequence of 6) as the HOST float[6] the C ABI takes."""
+    return _floats(6, v)
+
+
+def f3(v):
+    """A colour or point (tensor or sequence of 3) as a HOST float[3]."""
+    return _floats(3, v)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

@@ -149,6 +149,16 @@ class NGPradianceField(nn.Module):
             self._prep = (key, base16, col16)
         return self._prep[1], self._prep[2]
 
+    def density_ptrs(self):
+        """(table, w1, w2) as the C ABI takes them, into the fp16 copy of mlp_base.params: W1 [64][32], W2 [16][64], then the hash table."""
+        p = self._prepared()[0].data_ptr()
+        return p + 3072 * 2, p, p + 2048 * 2
+
+    def color_ptrs(self):
+        """(cw1, cw2, cw3) as the C ABI takes them, into the fp16 copy of color_mlp.params: [64][32], [64][64], [16][64]."""
+        p = self._prepared()[1].data_ptr()
+        return p, p + 2048 * 2, p + 6144 * 2
+
     def _aabb_host(self):
         """The six aabb floats on the host, cached against the buffer's version: `.tolist()` of a device tensor is a host sync."""
         c = self.__dict__.get("_aabb_cache")
@@ -163,7 +173,6 @@ class NGPradianceField(nn.Module):
         x_in_slot_order: x[j] is the position of point order[j] (then read contiguously)."""
         lib = L.load()
         import ctypes
-        base16, _ = self._prepared()
         x = x.reshape(-1, 3).contiguous().float()
         n = x.shape[0]
         density = torch.empty(n, dtype=torch.float32, device=x.device)
@@ -173,7 +182,7 @@ class NGPradianceField(nn.Module):
         # two-launch form (hash-grid levels pinned to the XCDs' L2s: csrc/ngp.hip); a handful of points through the fused kernel
         nws = int(lib.dreg_ngp_density_workspace_bytes(n)) if n >= 16384 else 0
         ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
-        L.check(lib.dreg_ngp_density_fwd_ws(L.ptr(x), base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+        L.check(lib.dreg_ngp_density_fwd_ws(L.ptr(x), *self.density_ptrs(),
                                             L.ptr(density), L.ptr(raw), *self._levels, aabb, n, int(bool(self.unbounded)), L.ptr(ws), nws,
                                             L.ptr(order) if order is not None else None, int(bool(x_in_slot_order and order is not None)), L.stream()),
                 "dreg_ngp_density_fwd_ws")
@@ -197,7 +206,6 @@ class NGPradianceField(nn.Module):
             raise NotImplementedError("query_density_grad: the gradient of the contracted (unbounded) field is not implemented")
         lib = L.load()
         import ctypes
-        base16, _ = self._prepared()
         shp = x.shape[:-1]
         x = x.reshape(-1, 3).contiguous().float()
         n = x.shape[0]
@@ -205,7 +213,7 @@ class NGPradianceField(nn.Module):
         grad = torch.empty(n, 3, dtype=torch.float32, device=x.device)
         mask = torch.empty(n, dtype=torch.int64, device=x.device) if return_mask else None
         aabb = (ctypes.c_float * 6)(*self._aabb_host())
-        L.check(lib.dreg_ngp_density_grad(L.ptr(x), base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+        L.check(lib.dreg_ngp_density_grad(L.ptr(x), *self.density_ptrs(),
                                           L.ptr(density), L.ptr(grad), L.ptr(mask), *self._levels, aabb, n, 0, L.stream()), "dreg_ngp_density_grad")
         out = (density.view(*shp, 1), grad.view(*shp, 3))
         return out + (mask.view(*shp),) if return_mask else out
@@ -228,11 +236,10 @@ class NGPradianceField(nn.Module):
     def query_rgb_mean(self, raw: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
         """Mean over the given viewing directions of the colour net's output: raw fp16 [N,16], dirs [K,3] -> [N,3] fp32."""
         lib = L.load()
-        _, col16 = self._prepared()
         n = raw.shape[0]
         rgb = torch.empty(n, 3, dtype=torch.float32, device=raw.device)
         bias = self.dir_bias(dirs)
-        L.check(lib.dreg_ngp_rgb_mean_fwd(L.ptr(raw.contiguous()), col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
+        L.check(lib.dreg_ngp_rgb_mean_fwd(L.ptr(raw.contiguous()), *self.color_ptrs(),
                                           L.ptr(bias), L.ptr(rgb), dirs.shape[0], n, L.stream()), "dreg_ngp_rgb_mean_fwd")
         return rgb
 
@@ -245,11 +252,10 @@ class NGPradianceField(nn.Module):
         d = dir.reshape(-1, 3).float().contiguous()
         feat = embedding.reshape(-1, self.geo_feat_dim)
         raw = torch.cat([torch.zeros(feat.shape[0], 1, device=feat.device, dtype=feat.dtype), feat], dim=1).half().contiguous()
-        _, col16 = self._prepared()
         n = raw.shape[0]
         assert d.shape[0] == n, f"{tuple(dir.shape)} v.s. {tuple(embedding.shape)}"
         rgb = torch.empty(n, 3, dtype=torch.float32, device=raw.device)
-        L.check(lib.dreg_ngp_rgb_dir_fwd(L.ptr(raw), col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2, L.ptr(d.to(raw.device)),
+        L.check(lib.dreg_ngp_rgb_dir_fwd(L.ptr(raw), *self.color_ptrs(), L.ptr(d.to(raw.device)),
                                          L.ptr(rgb), n, L.stream()), "dreg_ngp_rgb_dir_fwd")
         return rgb.view(*embedding.shape[:-1], 3).to(embedding.dtype)
 
@@ -504,7 +510,6 @@ class SampleGrid(nn.Module):
         world_slot = torch.empty(n, 3, dtype=torch.float32, device=dev)
         L.check(lib.dreg_grid_occupied_build(L.ptr(b8), L.ptr(ws), L.ptr(jitter), aabb, L.ptr(indices), L.ptr(order), L.ptr(world), L.ptr(world_slot),
                                              rx, ry, rz, n, L.stream()), "dreg_grid_occupied_build")
-        base16, _ = radiance_field._prepared()
         density = torch.empty(n, dtype=torch.float32, device=dev)
         raw = torch.empty(n, 16, dtype=torch.float16, device=dev)
         alpha = torch.empty(n, dtype=torch.float32, device=dev)
@@ -512,7 +517,7 @@ class SampleGrid(nn.Module):
         faabb = (ctypes.c_float * 6)(*radiance_field._aabb_host())
         nws = int(lib.dreg_ngp_density_workspace_bytes(n)) if n >= 16384 else 0
         dws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
-        L.check(lib.dreg_ngp_density_keep_fwd_ws(L.ptr(world_slot), base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
+        L.check(lib.dreg_ngp_density_keep_fwd_ws(L.ptr(world_slot), *radiance_field.density_ptrs(),
                                                  L.ptr(density), L.ptr(raw), *radiance_field._levels, faabb, n, int(bool(radiance_field.unbounded)),
                                                  L.ptr(dws), nws, L.ptr(order), 1, L.ptr(alpha), L.ptr(keep), float(self._delta), float(density_thre),
                                                  L.stream()), "dreg_ngp_density_keep_fwd_ws")

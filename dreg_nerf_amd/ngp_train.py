@@ -7,7 +7,6 @@
   NGPTrainer           the per-step rule: occupancy update every 16 steps, random rays over the block's images, render, smooth-L1 on the alive
                        rays, Adam, MultiStepLR, and the adaptive ray count that keeps 2^18 rendered samples per step
 """
-import ctypes
 import math
 from typing import Optional
 
@@ -28,10 +27,6 @@ def render_step_size_of(aabb) -> float:
     return max(a[3] - a[0], a[4] - a[1], a[5] - a[2]) * math.sqrt(3) / 1024
 
 
-def _f6(v):
-    return (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
-
-
 class _RenderTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, base_params, color_params, field, occupancy_grid, o, d, jitter, scene_aabb, dt, bkgd, alpha_thre):
@@ -45,10 +40,9 @@ class _RenderTrain(torch.autograd.Function):
         depth = torch.empty(n, dtype=torch.float32, device=dev)
         counters = torch.zeros(2, dtype=torch.int64, device=dev)
         L.check(lib.dreg_ngp_render_train(L.ptr(o), L.ptr(d), L.ptr(jitter), n, L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
-                                          base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
-                                          col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
-                                          *field._levels, _f6(roi), _f6(scene_aabb), _f6(field._aabb_host()), -math.inf, math.inf,
-                                          float(dt), float(alpha_thre), 1e-4, (ctypes.c_float * 3)(*bkgd),
+                                          *field.density_ptrs(), *field.color_ptrs(),
+                                          *field._levels, L.f6(roi), L.f6(scene_aabb), L.f6(field._aabb_host()), -math.inf, math.inf,
+                                          float(dt), float(alpha_thre), 1e-4, L.f3(bkgd),
                                           L.ptr(rgb), L.ptr(opacity), L.ptr(depth), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
                 "dreg_ngp_render_train")
         c = counters.cpu()                      # the step's one readback: the surviving samples (next step's ray count)
@@ -75,7 +69,7 @@ class _RenderTrain(torch.autograd.Function):
             nws = int(lib.dreg_ngp_render_bwd_workspace_bytes(n))
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
             L.check(lib.dreg_ngp_render_bwd(L.ptr(o), L.ptr(d), L.ptr(jitter), n, L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
-                                            base16.data_ptr(), col16.data_ptr(), *field._levels, _f6(roi), _f6(ctx.scene_aabb), _f6(field._aabb_host()),
+                                            base16.data_ptr(), col16.data_ptr(), *field._levels, L.f6(roi), L.f6(ctx.scene_aabb), L.f6(field._aabb_host()),
                                             -math.inf, math.inf, ctx.dt, ctx.alpha_thre, 1e-4, L.ptr(rgb), L.ptr(g_rgb.float().contiguous()),
                                             L.ptr(grad_base), L.ptr(grad_color), L.ptr(ws), nws, L.stream()), "dreg_ngp_render_bwd")
         return grad_base, grad_color, None, None, None, None, None, None, None, None, None

@@ -10,7 +10,6 @@ A registered pair of blocks as ONE scene goes through the fused two-block kernel
 render_pair_views, and render_scene_merged for eval_nerf_regtr.py --render_merged; rule: DESIGN.md §3e, CPU restatement:
 tests/render_pair_restatement.py)."""
 import collections
-import ctypes
 import math
 import os
 import shutil
@@ -116,7 +115,6 @@ def _render(field, occupancy_grid, rays, scene_aabb, near_plane, far_plane, rend
     d = rays.viewdirs.reshape(-1, 3).to(dev).float().contiguous()
     n = o.shape[0]
     roi, b8, bits = _grid_parts(occupancy_grid, dev)
-    f6 = lambda v: (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
     bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(v) for v in torch.as_tensor(render_bkgd).reshape(-1).tolist()]
     rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
     opacity = torch.empty(n, dtype=torch.float32, device=dev)
@@ -124,11 +122,10 @@ def _render(field, occupancy_grid, rays, scene_aabb, near_plane, far_plane, rend
     counters = torch.zeros(2, dtype=torch.int64, device=dev)          # surviving samples, then the ray queue
     visibility.OVERRUN.check()
     L.check(lib.dreg_ngp_render(L.ptr(o), L.ptr(d), n, L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
-                                base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
-                                col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
-                                *field._levels, f6(roi), f6(scene_aabb), f6(field._aabb_host()),
+                                *field.density_ptrs(), *field.color_ptrs(),
+                                *field._levels, L.f6(roi), L.f6(scene_aabb), L.f6(field._aabb_host()),
                                 -math.inf if near_plane is None else float(near_plane), math.inf if far_plane is None else float(far_plane),
-                                float(render_step_size), float(alpha_thre or 0.0), 1e-4, (ctypes.c_float * 3)(*bk),
+                                float(render_step_size), float(alpha_thre or 0.0), 1e-4, L.f3(bk),
                                 L.ptr(rgb), L.ptr(opacity), L.ptr(depth), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
             "dreg_ngp_render")
     visibility.OVERRUN.watch(counters[1:])
@@ -168,15 +165,11 @@ def _pair_block_args(field, grid, rays, opts, center, dev, keep):
     o = rays.origins.reshape(-1, 3).to(dev).float().contiguous()
     d = rays.viewdirs.reshape(-1, 3).to(dev).float().contiguous()
     roi, b8, bits = _grid_parts(grid, dev)
-    f6 = lambda v: (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
     near, far = opts.get("near_plane"), opts.get("far_plane")
-    c3 = (ctypes.c_float * 3)(*[float(v) for v in torch.as_tensor(center).reshape(-1).tolist()])
-    arrs = [f6(roi), f6(opts["scene_aabb"]), f6(field._aabb_host()), c3]
+    arrs = [L.f6(roi), L.f6(opts["scene_aabb"]), L.f6(field._aabb_host()), L.f3(torch.as_tensor(center))]
     keep.extend([o, d, b8, bits, base16, col16] + arrs)
     return [L.ptr(o), L.ptr(d), L.ptr(b8), b8.shape[0], b8.shape[1], b8.shape[2], L.ptr(bits),
-            base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
-            col16.data_ptr(), col16.data_ptr() + 2048 * 2, col16.data_ptr() + 6144 * 2,
-            *field._levels, arrs[0], arrs[1], arrs[2],
+            *field.density_ptrs(), *field.color_ptrs(), *field._levels, arrs[0], arrs[1], arrs[2],
             -math.inf if near is None else float(near), math.inf if far is None else float(far),
             float(opts.get("render_step_size", 1e-3)), float(opts.get("alpha_thre") or 0.0), arrs[3]]
 
@@ -216,7 +209,7 @@ def render_pair_image(src_field, src_grid, tgt_field, tgt_grid, rays, pose, src_
         opacity, depth, wsrc = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
         counters = torch.zeros(2, dtype=torch.int64, device=dev)          # surviving samples, then the ray queue
         visibility.OVERRUN.check()
-        L.check(lib.dreg_ngp_render_pair(n, *src_args, *tgt_args, float(power), 1e-4, (ctypes.c_float * 3)(*bk),
+        L.check(lib.dreg_ngp_render_pair(n, *src_args, *tgt_args, float(power), 1e-4, L.f3(bk),
                                          L.ptr(rgb), L.ptr(opacity), L.ptr(depth), L.ptr(wsrc), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
                 "dreg_ngp_render_pair")
         visibility.OVERRUN.watch(counters[1:])

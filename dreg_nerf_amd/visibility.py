@@ -5,7 +5,6 @@ step (train_nerf_regtr.py:186-199 -> conerf/loss/confidence_loss.py:56-160) and 
 The reference re-loads the block checkpoint from disk twice per call (confidence_loss.py:34-35,50); here loaded blocks are
 cached per path."""
 import collections
-import ctypes
 import threading
 from typing import Dict, List
 
@@ -185,17 +184,14 @@ def surface_visibility(points: torch.Tensor, cam_centres: torch.Tensor, field: n
                        alpha_thre: float = 0.0, coarse_bits: torch.Tensor = None) -> torch.Tensor:
     """points [Np,3], cam_centres [Nc,3] (device) -> bool [Np]: visible from at least one camera with surface field >= cut_off."""
     lib = L.load()
-    base16, _ = field._prepared()
     pts = points.reshape(-1, 3).contiguous().float()
     cams = cam_centres.reshape(-1, 3).contiguous().float().to(pts.device)
     # labels [Np] int32 followed by the ray queue's counter (8 bytes) in one zeroed buffer
     buf = torch.zeros(pts.shape[0] + 2 + (pts.shape[0] & 1), dtype=torch.int32, device=pts.device)
     label = buf[:pts.shape[0]]
     b8 = binary if binary.dtype == torch.uint8 and binary.is_contiguous() else (binary.contiguous().view(torch.uint8) if binary.dtype == torch.bool else binary.to(torch.uint8).contiguous())
-    f6 = lambda v: (ctypes.c_float * 6)(*[float(t) for t in (v.tolist() if torch.is_tensor(v) else v)])
     common = (L.ptr(cams), L.ptr(pts), L.ptr(b8), L.ptr(label),
-              base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
-              *field._levels, f6(roi_aabb), f6(scene_aabb), f6(field._aabb_host()),
+              *field.density_ptrs(), *field._levels, L.f6(roi_aabb), L.f6(scene_aabb), L.f6(field._aabb_host()),
               b8.shape[0], b8.shape[1], b8.shape[2], cams.shape[0], pts.shape[0],
               float(render_step_size), float(cut_off), float(early_stop_eps), float(alpha_thre))
     if PERSISTENT:     # lanes refilled from a ray queue, labelled points not marched again (csrc/visibility.hip)
@@ -342,17 +338,15 @@ def compute_visibility_scores_batched(requests, cut_off: float = 0.5, max_waves:
     nb = int(lib.dreg_surface_visibility_desc_bytes())
     host, host_ev = _desc_staging(len(requests) * nb, device)
     host = host[:len(requests) * nb].view(len(requests), nb)
-    f6 = lambda v: (ctypes.c_float * 6)(*[float(t) for t in v])
     keep, total = [], 0
     for i, ((xyz, _), (field, _, meta)) in enumerate(zip(requests, blocks)):
         pts = xyz.reshape(-1, 3).contiguous().float()
         keep.append(pts)
-        base16, _ = field._prepared()
         b8, cams = meta["binary_u8"], meta["cam_centres_dev"]
         total += cams.shape[0] * pts.shape[0]
         L.check(lib.dreg_surface_visibility_fill_desc(host[i].data_ptr(), L.ptr(cams), L.ptr(pts), L.ptr(b8), buf.data_ptr() + 4 * lab_off[i],
-                                                      base16.data_ptr() + 3072 * 2, base16.data_ptr(), base16.data_ptr() + 2048 * 2,
-                                                      *field._levels, f6(meta["aabb_host"]), f6(meta["aabb_host"]), f6(field._aabb_host()),
+                                                      *field.density_ptrs(), *field._levels,
+                                                      L.f6(meta["aabb_host"]), L.f6(meta["aabb_host"]), L.f6(field._aabb_host()),
                                                       b8.shape[0], b8.shape[1], b8.shape[2], cams.shape[0], pts.shape[0],
                                                       float(meta["render_step_size"]), float(cut_off), 1e-4, float(meta.get("alpha_thre", 0.0) or 0.0),
                                                       buf.data_ptr() + 4 * (q_off + 2 * i), L.ptr(meta["coarse_bits"]) if COARSE else None),
