@@ -57,6 +57,7 @@ struct Op {
     int sstem_conv = -1, sstem_lat = -1;   //   that convolution; the active-set convolution that also reads the activation (-1: none)
     size_t xam_off = 0, pmask_off = 0;     //   raw x of the arg-max voxels [B,Do,Ho,Wo,C] bf16; pooled-window flags
     int halo = 0;                // OP_CONV: bit 0 = forward, bit 1 = data gradient run on the halo kernel
+    int pointwise = 0;           // OP_CONV: bit 0 = forward, bit 1 = plain data gradient, bit 2 = accumulating data gradient run on the streaming 1^3 kernel (conv_pointwise.hip)
     int stats_bn = -1;           // OP_CONV whose bf16 output feeds a large-path BatchNorm: that op's index (its chunk sums come from this convolution's epilogue)
     size_t stats_off = 0;        // OP_BN with such a producer: its own chunk-sum buffer [B][V / 128][C][2] (the shared workspace may be used in between)
     int stats_conv = -1;
@@ -178,7 +179,7 @@ void dreg_exec_default_opts(dreg_exec_opts* o)
 {
     std::memset(o, 0, sizeof(*o));
     o->sparse_grads = 1; o->bn_batch_tails = 1; o->fuse_stem = 1; o->sparse_stem = 1; o->fold_res_bn = 1; o->fold_splitk = 1;
-    o->group_wgrad = 1; o->s2_accumulate = 1; o->fuse_bn_stats = 1; o->brick = 1; o->defer_head_pg = 0;
+    o->group_wgrad = 1; o->s2_accumulate = 1; o->fuse_bn_stats = 1; o->brick = 1; o->defer_head_pg = 0; o->pointwise_stream = 1;
 }
 void* dreg_exec_create(const int* tensors, int nt, const int* ops, int nops, const int64_t* params, int np)
 {
@@ -507,6 +508,17 @@ void* dreg_exec_create_opts(const int* tensors, int nt, const int* ops, int nops
             if (on(p.d0) && p.d1 % 16 == 0 && p.pk_brick_fwd == SIZE_MAX) p.pk_brick_fwd = add_brick_pack(p, 0);
             if (e->needs_grad[o.in] && on(p.d1) && p.d0 % 16 == 0 && p.pk_brick_dgrad == SIZE_MAX) p.pk_brick_dgrad = add_brick_pack(p, 1);
         }
+        if (o.kind == OP_CONV && e->opt.pointwise_stream && o.rows_out < 0 && !o.halo) {
+            // dense 1^3 stride-1 layers of the large levels: the streaming kernel reads the implicit GEMM's packs (bit-identical, so the rule may look at the size)
+            const bool same = x.D == y.D && x.H == y.H && x.W == y.W;
+            const bool add_ok = o.in2 < 0 || (o.add_same && e->t[o.in2].D == y.D && e->t[o.in2].H == y.H && e->t[o.in2].W == y.W);
+            if (same && add_ok && !o.fold_sk_fwd && p.d1 == x.C &&
+                dreg_conv1_stream_use(x.B, y.D, y.H, y.W, x.C, p.d0, o.ksz, o.stride, o.pad, o.relu, o.in2 >= 0, o.add_same, 0, 0)) o.pointwise |= 1;
+            if (same && e->needs_grad[o.in] && !s2_class_ok(p, o.ksz, o.stride, o.pad)) {
+                if (!o.fold_sk_bwd && dreg_conv1_stream_use(x.B, x.D, x.H, x.W, p.d0, p.d1, o.ksz, o.stride, o.pad, 0, 0, 1, 0, 0)) o.pointwise |= 2;
+                if (dreg_conv1_stream_use(x.B, x.D, x.H, x.W, p.d0, p.d1, o.ksz, o.stride, o.pad, 0, 1, 1, 0, 0)) o.pointwise |= 4;
+            }
+        }
         if (o.halo & 1) { if (p.pk_halo_fwd == SIZE_MAX) p.pk_halo_fwd = add_halo_pack(p, 0); }
         else if (p.pk_fwd == SIZE_MAX) { p.cin_pad = x.C; p.pk_fwd = add_pack(p, 0, x.C); }
         if (e->needs_grad[o.in]) {
@@ -564,6 +576,11 @@ int dreg_exec_repack(void* h, const void* descs_dev, const int* row_desc_dev, vo
 }
 // bit 0 / bit 1: the forward / data gradient of op `op` runs on the halo kernel (labels of the HIP-event timing records)
 int dreg_exec_op_halo(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].halo : 0; }
+// 1: the weight gradient of op `op` belongs to the grouped launch of an un-bracketed whole backward pass (dreg_exec_opts.group_wgrad): under
+// dreg_exec_set_timing it is launched (and bracketed) alone, so its record names no row of a steady-state kernel trace
+int dreg_exec_op_wgrad_grouped(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].grp : 0; }
+// bit 0 / 1 / 2: the forward / plain data gradient / accumulating data gradient of op `op` runs on the streaming 1^3 kernel
+int dreg_exec_op_pointwise(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].pointwise : 0; }
 
 // 1 (default): weight / bias gradients on the executor's own second stream, overlapping the data-gradient chain; 0: one stream
 void dreg_exec_set_overlap(void* h, int enable) { ((Exec*)h)->use_aux = enable != 0; }
@@ -738,6 +755,17 @@ int dreg_exec_forward(void* h, void* arena, size_t arena_bytes, const void* pack
                 else
                     CK(dreg_conv3_halo_n(act(o.in), PK + w.pk_halo_fwd, act(o.out), bias, add, x.B, x.D, x.H, x.W, x.C, w.d0, ta ? ta->D : 0, ta ? ta->H : 0, ta ? ta->W : 0,
                                          o.add_same, 0, stream));
+                continue;
+            }
+            if (o.pointwise & 1) {
+                if (train && o.stats_bn >= 0)
+                    CK(dreg_conv1_stream_bnstats(act(o.in), PK + w.pk_fwd, act(o.out), bias, add, x.B, x.D, x.H, x.W, x.C, y.D, y.H, y.W, w.d0,
+                                                 o.ksz, o.stride, o.pad, o.relu, ta ? ta->D : 0, ta ? ta->H : 0, ta ? ta->W : 0, o.add_same,
+                                                 A + e->off_ks, e->sz_ks, (float*)(A + e->ops[o.stats_bn].stats_off), &sums_rpc[o.stats_bn], stream, 0));
+                else
+                    CK(dreg_conv1_stream(act(o.in), PK + w.pk_fwd, act(o.out), bias, add, x.B, x.D, x.H, x.W, x.C, y.D, y.H, y.W, w.d0,
+                                         o.ksz, o.stride, o.pad, 0, o.relu, ta ? ta->D : 0, ta ? ta->H : 0, ta ? ta->W : 0, o.add_same, 0, 0,
+                                         A + e->off_ks, e->sz_ks, stream, 0));
                 continue;
             }
             if (train && o.stats_bn >= 0 && !(o.in == 0 && e->in_rowocc)) {
@@ -1109,6 +1137,10 @@ int dreg_exec_backward_range(void* h, void* arena, size_t arena_bytes, const voi
                     CK(dreg_conv3d_dgrad_s2_acc(gy, PK + w.pk_cls, gx, x.B, x.D, x.H, x.W, x.C, y.D, y.H, y.W, w.d0, o.ksz, o.pad, stream));
                 } else if (fused_add) {
                     sc.variant(1);        // dispatched WITH an addend (igemm_choose may pick another tile for it)
+                    if (o.pointwise & 4)
+                        CK(dreg_conv1_stream(gy, PK + w.pk_dgrad, gx, nullptr, gx, x.B, y.D, y.H, y.W, w.d0, x.D, x.H, x.W, w.d1,
+                                             o.ksz, o.stride, o.pad, 1, 0, x.D, x.H, x.W, 1, 0, 0, A + e->off_ks, e->sz_ks, stream, 0));
+                    else
                     CK(dreg_conv3d_igemm_ws(gy, PK + w.pk_dgrad, gx, nullptr, gx, x.B, y.D, y.H, y.W, w.d0, x.D, x.H, x.W, w.d1,
                                             o.ksz, o.stride, o.pad, 1, 0, x.D, x.H, x.W, 1, 0, 0, A + e->off_ks, e->sz_ks, stream));
                 } else if (rows) {
@@ -1137,7 +1169,10 @@ int dreg_exec_backward_range(void* h, void* arena, size_t arena_bytes, const voi
                         CK(dreg_conv3d_igemm_defer(gy, PK + w.pk_dgrad, gx, nullptr, nullptr, x.B, y.D, y.H, y.W, w.d0, x.D, x.H, x.W, w.d1,
                                                    o.ksz, o.stride, o.pad, 1, 0, 0, 0, 0, 0, A + e->off_ks, e->sz_ks, nullptr, &ns, &sl, stream));
                         if (ns > 0) { e->pend_sk_bn = i - 1; e->pend_sk_n = ns; e->pend_sk_slice = sl; }
-                    } else
+                    } else if (o.pointwise & 2)
+                        CK(dreg_conv1_stream(gy, PK + w.pk_dgrad, gx, nullptr, nullptr, x.B, y.D, y.H, y.W, w.d0, x.D, x.H, x.W, w.d1,
+                                             o.ksz, o.stride, o.pad, 1, 0, 0, 0, 0, 0, 0, 0, A + e->off_ks, e->sz_ks, stream, 0));
+                    else
                     CK(dreg_conv3d_igemm_ws(gy, PK + w.pk_dgrad, gx, nullptr, nullptr, x.B, y.D, y.H, y.W, w.d0, x.D, x.H, x.W, w.d1,
                                             o.ksz, o.stride, o.pad, 1, 0, 0, 0, 0, 0, 0, 0, A + e->off_ks, e->sz_ks, stream));
                 }

@@ -74,6 +74,12 @@ SIGNATURES = {
     "dreg_conv3_halo_pack_bytes_n": (Z, [I, I]),
     "dreg_conv3_halo_n": (I, [P, P, P, P, P] + [I] * 11 + [P]),
     "dreg_conv3_halo_n_bnstats": (I, [P, P, P, P, P] + [I] * 10 + [P, P, P]),
+    # conv_pointwise.hip
+    "dreg_conv1_stream_variant": (I, [I, I]),
+    "dreg_conv1_stream_supported": (I, [I] * 14),
+    "dreg_conv1_stream_use": (I, [I] * 14),
+    "dreg_conv1_stream": (I, [P, P, P, P, P] + [I] * 20 + [P, Z, P, I]),
+    "dreg_conv1_stream_bnstats": (I, [P, P, P, P, P] + [I] * 17 + [P, Z, P, P, P, I]),
     "dreg_conv3d_wgrad_variant": (I, [I] * 10),
     "dreg_conv3d_igemm_variant": (I, [I] * 17),
     "dreg_conv3d_wgrad_group_fill": (I, [P, P, P, P, Z] + [I] * 12 + [P, P]),
@@ -131,6 +137,8 @@ SIGNATURES = {
     "dreg_exec_create": (P, [P, I, P, I, P, I]),
     "dreg_exec_destroy": (None, [P]),
     "dreg_exec_op_halo": (I, [P, I]),
+    "dreg_exec_op_pointwise": (I, [P, I]),
+    "dreg_exec_op_wgrad_grouped": (I, [P, I]),
     "dreg_exec_arena_bytes": (Z, [P]),
     "dreg_exec_pack_bytes": (Z, [P]),
     "dreg_exec_num_packs": (I, [P]),
@@ -315,7 +323,7 @@ _probe_lib = None
 class ExecOpts(ctypes.Structure):
     """dreg_exec_opts of include/dreg_nerf.h (creation options of one trunk executor)."""
     _fields_ = [(n, c_int) for n in ("sparse_grads", "bn_batch_tails", "fuse_stem", "sparse_stem", "fold_res_bn", "fold_splitk", "group_wgrad",
-                                     "s2_accumulate", "fuse_bn_stats", "brick", "defer_head_pg", "persistent_deep", "guard")] + [("reserved", c_int * 3)]
+                                     "s2_accumulate", "fuse_bn_stats", "brick", "defer_head_pg", "persistent_deep", "guard", "pointwise_stream")] + [("reserved", c_int * 2)]
 
 
 def load_probe():

@@ -217,6 +217,13 @@ class TrunkExecutor:
                 fname = "conv3_halo64_kernel<bf16>" if cout == 64 else "conv3_halo_kernel<bf16>"
             if halo & 2:
                 dname = "conv3_halo64_kernel<bf16>" if x[4] == 64 else "conv3_halo_kernel<bf16>"
+            pw = self.lib.dreg_exec_op_pointwise(self.h, i)       # the streaming 1^3 kernel (csrc/conv_pointwise.hip): forward / plain / accumulating data gradient
+            if pw & 1:
+                fname = f"conv1_stream_kernel<{x[4]},{lib.dreg_conv1_stream_variant(x[4], cout)}>"
+            if pw & 2:
+                dname = f"conv1_stream_kernel<{cout},{lib.dreg_conv1_stream_variant(cout, x[4])}>"
+            if pw & 4:
+                dname_add = f"conv1_stream_kernel<{cout},{lib.dreg_conv1_stream_variant(cout, x[4])}>"
             rows = "-rows" if is_rows else ""
             fl = 2.0 * M * cout * k ** 3 * cin
             # active-set launches: flops per row, scaled by the step's row count (list id) when the records are drained
@@ -227,6 +234,10 @@ class TrunkExecutor:
             def wgrad_name(nr, B=B, x=x, y=y, cout=cout, k=k, is_rows=is_rows, first=int(o[1] == 0)):
                 return ops.wgrad_kernel_name(lib, B, y[1], y[2], y[3], x[4], cout, k, is_rows, nr, first)
             wname = wgrad_name if is_rows else wgrad_name(0)
+            if not is_rows and self.lib.dreg_exec_op_wgrad_grouped(self.h, i):
+                # every un-bracketed step runs this layer inside the grouped launch: the lone launch of a bracketed step is no row of a steady-state
+                # kernel trace, so (like '...+reduce') the record does not stand for a single kernel whose launches per step can be counted
+                wname = wname + "+grouped"
             out[(i, 2)] = (wname, f"wgrad{rows} B{B} {x[1]}x{x[2]}x{x[3]}x{x[4]} g{y[1]}x{y[2]}x{y[3]}x{cout} k{k}s{s}", fl, lo, per_row, None, None)
         out[(-1, 3)] = ("wgrad_reduce_batched_kernel", "split sums of a backward range -> torch-layout gradients", 0.0, -1, 0.0, None, None)
         out[(-1, 4)] = ("bn_tail_batched_kernel<0>", "running statistics of the small BatchNorms of a forward pass", 0.0, -1, 0.0, None, None)

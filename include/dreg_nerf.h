@@ -120,6 +120,31 @@ int dreg_conv3_halo_n(const void* in, const void* wpk, void* out, const float* b
 int dreg_conv3_halo_n_bnstats(const void* in, const void* wpk, void* out, const float* bias, const void* addend,
                               int B, int D, int H, int W, int Cin, int Cout, int Da, int Ha, int Wa, int add_same, float* bn_partial, int* rows_per_chunk, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- streaming 1x1x1 convolution (csrc/conv_pointwise.hip)
+ * The dense 1^3 stride-1 bf16 convolutions of the large levels are byte movers; this kernel family streams them: a workgroup walks a range of
+ * 128-row chunks with its weight slice in registers and requests the next tile's input / addend rows before the current tile's MFMAs and stores.
+ * It reads the packs of dreg_pack_conv_weight (forward or data-gradient) and writes, BIT FOR BIT, what dreg_conv3d_igemm_ws / _bnstats write.
+ * dreg_conv1_stream_supported: the kernel can run this launch — bf16 (dtype 0), dense rows (nrows 0), ksz 1, stride 1, pad 0, relu 0 / 1, no addend or a
+ *   same-size one (add_same), a (Cin, Cout) pair with an instantiation (64 -> 64 | 128 k, 128 -> 128 k, 256 -> 64 | 128 k), operands below 0x7fffff00 bytes.
+ * dreg_conv1_stream_use: ... and it is the faster launch (profiles/pw_stream_by_shape.txt: every instantiation from 32^3 voxels per grid on, 128 | 256 -> 512
+ *   from 16^3 on; independent of B) — the executor's rule.
+ * dreg_conv1_stream / _bnstats: the arguments of dreg_conv3d_igemm_ws / dreg_conv3d_igemm_bnstats plus max_blocks (0 = automatic; else the number of
+ *   workgroups per channel slice).  Launches the kernel cannot run go to those entry points.  *rows_per_chunk = 128 when V % 128 == 0, else 0. */
+ /* dreg_conv1_stream_variant: BN of the instantiation conv1_stream_kernel<Cin, BN, ...> that serves (Cin, Cout), 0 = none (profiler labels) */
+int dreg_conv1_stream_variant(int Cin, int Cout);
+int dreg_conv1_stream_supported(int B, int D, int H, int W, int Cin, int Cout, int ksz, int stride, int pad, int relu,
+                                int has_addend, int add_same, int dtype, int nrows);
+int dreg_conv1_stream_use(int B, int D, int H, int W, int Cin, int Cout, int ksz, int stride, int pad, int relu,
+                          int has_addend, int add_same, int dtype, int nrows);
+int dreg_conv1_stream(const void* in, const void* wt_packed, void* out, const float* bias, const void* addend,
+                      int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                      int ksz, int stride, int pad, int transposed, int relu, int Da, int Ha, int Wa, int add_same,
+                      int dtype, int out_f32, void* workspace, size_t workspace_bytes, void* stream, int max_blocks);
+int dreg_conv1_stream_bnstats(const void* in, const void* wt_packed, void* out, const float* bias, const void* addend,
+                              int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                              int ksz, int stride, int pad, int relu, int Da, int Ha, int Wa, int add_same,
+                              void* workspace, size_t workspace_bytes, float* bn_partial, int* rows_per_chunk, void* stream, int max_blocks);
+
 /* Data gradient of a stride-2 convolution (ksz 3 / pad 1: resnet3d.py conv2 of the first block of layer2-4; ksz 1 / pad 0: the
  * downsample branch) without the 7/8 structurally-zero taps of the gather form: ONE 2^3-tap convolution over dOut whose
  * 8 x Cin output channels are the 8 parity classes of dIn (scattered in place by the epilogue).  bf16 only;
@@ -414,7 +439,9 @@ typedef struct dreg_exec_opts {
     int guard;            /* debug: 1 = every region of the arena (each activation, statistic, gradient, row-list copy, scratch buffer) is followed by a 64 KiB
                              poisoned guard band (dreg_exec_guard_check scans them); 2 = forward / backward additionally scan after EVERY op (stream
                              synchronisation per op) and return DREG_EGUARD at the first op behind which a band has changed (dreg_exec_guard_last) */
-    int reserved[3];
+    int pointwise_stream; /* 1 (default): dense 1^3 stride-1 convolutions (forward, data gradient, accumulating data gradient) that dreg_conv1_stream_use admits
+                             run on csrc/conv_pointwise.hip (bit-identical); 0: the implicit GEMM */
+    int reserved[2];
 } dreg_exec_opts;
 void dreg_exec_default_opts(dreg_exec_opts* o);
 void* dreg_exec_create_opts(const int* tensors, int nt, const int* ops, int nops, const int64_t* params, int np, const dreg_exec_opts* opts);
@@ -436,6 +463,8 @@ int dreg_exec_pack_rows(void* h);
 int dreg_exec_export_pack_table(void* h, void* host_out, int* host_row_desc, void* pack_base);   /* 48-byte records + row->record map */
 int dreg_exec_repack(void* h, const void* descs_dev, const int* row_desc_dev, void* stream);
 int dreg_exec_op_halo(void* h, int op);   /* bit 0 / 1: forward / data gradient of convolution `op` runs on the halo kernel (dreg_conv3_halo_use) */
+int dreg_exec_op_wgrad_grouped(void* h, int op);   /* 1: the weight gradient of convolution `op` is part of the grouped launch (group_wgrad) except under dreg_exec_set_timing, where it is launched and bracketed alone */
+int dreg_exec_op_pointwise(void* h, int op);   /* bit 0 / 1 / 2: forward / plain data gradient / accumulating data gradient of convolution `op` runs on the streaming 1^3 kernel (dreg_conv1_stream_use) */
 void dreg_exec_set_overlap(void* h, int enable);
 void dreg_exec_set_input_row_occupancy(void* h, const uint8_t* rowocc);   /* flags for the convolution that reads x_in (the stem); null = none */                             /* 1 (default): weight gradients on aux_stream */
 void dreg_exec_set_timing(void* h, int enable);                              /* HIP events around every convolution launch */
