@@ -84,6 +84,10 @@ def config_parser(argv=None):
     p.add_argument("--merged_mesh", action="store_true",
                    help="eval_nerf_regtr.py: per scene whose block checkpoints are on disk, write merged_mesh_pred.ply and merged_mesh_gt.ply: the source block's mesh "
                         "moved by the predicted / the known pose, concatenated with the target block's")
+    p.add_argument("--merged_mesh_field", action="store_true",
+                   help="eval_nerf_regtr.py: per scene whose block checkpoints are on disk, mesh the registered pair as ONE density field (fused pair-density "
+                        "kernel, DESIGN.md 3i; --mesh_resolution cells on the pair's longest axis, --mesh_level) under the predicted and the known pose: "
+                        "merged_field_mesh_pred.ply, merged_field_mesh_gt.ply and merged_field_mesh.json (V, F, area, volume of both)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

@@ -3,7 +3,8 @@
 (:224-301; with --dump_outputs also its per-scene transformation_est.json and PLY point clouds, :313-438; with --render_views the renders of
 both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369; with --render_merged, which the reference lacks,
 both blocks rendered as one scene under the ground-truth and the predicted pose and merged_metrics.json; with --merged_mesh the two
-blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / merged_mesh_gt.ply): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / merged_mesh_gt.ply; with --merged_mesh_field the pair meshed as ONE density field, one closed surface per pose,
+merged_field_mesh_pred.ply / merged_field_mesh_gt.ply / merged_field_mesh.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -125,7 +126,7 @@ def main():
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows, refined_rows = {}, {}, {}
     ransac_rows, ransac_refined_rows = {}, {}
-    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged or cfg.merged_mesh
+    per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged or cfg.merged_mesh or cfg.merged_mesh_field
     mine = ES.my_scenes(len(ds), rank, world)
     # every rank consumes the block-order draws of ALL scenes in scene order: a scene's source / target assignment is then the one-rank run's,
     # whatever the rank count — the gathered metrics file does not depend on the sharding (dreg_nerf_amd/eval_shard.py)
@@ -203,6 +204,16 @@ def main():
                           f"F {mm['tgt']['faces'].shape[0]} -> {scene_dir}/merged_mesh_{{pred,gt}}.ply", flush=True)
                 else:
                     print(f"{data['scene']}: no NeRF blocks on disk, merged mesh not written", flush=True)
+            if cfg.merged_mesh_field:   # the pair as ONE density field (the scene --render_merged renders), one closed surface per pose
+                sp, tp = data.get("src_nerf_path", ""), data.get("tgt_nerf_path", "")
+                if sp and tp and os.path.exists(sp) and os.path.exists(tp):
+                    from dreg_nerf_amd.pair_field import merged_field_scene_mesh
+                    st = merged_field_scene_mesh(scene_dir, sp, tp, data["pose"][0], pred["pose"][-1][0], dev, cfg.mesh_resolution, cfg.mesh_level)["stats"]
+                    print(f"{data['scene']}: merged field mesh, pred V {st['pred']['V']} F {st['pred']['F']} area {st['pred']['area']:.4f} volume {st['pred']['volume']:.4f}, "
+                          f"gt V {st['gt']['V']} F {st['gt']['F']} area {st['gt']['area']:.4f} volume {st['gt']['volume']:.4f} -> {scene_dir}/merged_field_mesh_{{pred,gt}}.ply",
+                          flush=True)
+                else:
+                    print(f"{data['scene']}: no NeRF blocks on disk, merged field mesh not written", flush=True)
             if cfg.fgr_baseline:   # the reference's baseline on the two voxel point clouds (global_registration.py:96-116)
                 T, sec = fgr.run_registration(_points(data, "src"), _points(data, "tgt"))
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])

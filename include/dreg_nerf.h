@@ -897,6 +897,29 @@ int dreg_mc_count(const float* values, int nx, int ny, int nz, float level, void
 int dreg_mc_emit(const float* values, int nx, int ny, int nz, float level, const float* origin, const float* spacing, const void* workspace,
                  size_t workspace_bytes, float* verts, int* faces, int V, int F, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- a registered pair of blocks as one density field
+ * (csrc/pair_field.hip; rule: DESIGN.md §3i) The density of the scene dreg_ngp_render_pair renders, at points of the TARGET frame: a block
+ * contributes where its OWN occupancy cell is set, and where both do they share the point by §3e's overlap weight.  Points form: x fp32 [n,3] on
+ * the device, origin = spacing = null.  Lattice form: x = null (n is ignored), origin / spacing: 3 fp32 each in HOST memory, node (ix,iy,iz) at
+ * origin[c] + (float)i_c * spacing[c] (dreg_mc_emit's position of the node), outputs [nz,ny,nx] with x fastest; no position buffer exists.
+ * Per block (src_*, tgt_*): binary uint8 [rx,ry,rz] over roi_aabb, the density net and the five level arrays as for dreg_ngp_density_fwd,
+ * model_aabb, and center = the centroid of the block's cameras in its own frame; aabbs, level arrays and centers in HOST memory.  pose: 12 fp32
+ * in HOST memory (R row-major, then t; source -> target, the caller's fp64 pose rounded once).  power: the exponent p of the overlap weight.
+ * Outputs on the device: sigma fp32 [n]; optional (null = not written) w_src, w_tgt (the blocks' weights: 0, 1, or w and 1 - w where both cover
+ * the point), sigma_src, sigma_tgt (m_b ? sigma_b : 0; the blocks' dense-query densities bit for bit) fp32 [n];
+ * sigma = fl(fl(w_src sigma_src) + fl(w_tgt sigma_tgt)).  One launch on `stream`, no atomics, never allocates: identical bytes between runs,
+ * point orders and the two forms.  DREG_EINVAL before any launch: a null required pointer, n < 0, both forms at once, a lattice dimension < 2 or
+ * > 1024 or more than 2^28 nodes, a power that is not finite and positive, an occupancy-grid dimension <= 0.  Points form with n == 0: DREG_OK,
+ * nothing is launched. */
+int dreg_pair_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz,
+                      const uint8_t* src_binary, int src_rx, int src_ry, int src_rz, const void* src_table, const void* src_w1, const void* src_w2,
+                      const uint32_t* src_offset, const uint32_t* src_size, const uint32_t* src_res, const float* src_scale, const uint32_t* src_hashed,
+                      const float* src_roi_aabb, const float* src_model_aabb, const float* src_center,
+                      const uint8_t* tgt_binary, int tgt_rx, int tgt_ry, int tgt_rz, const void* tgt_table, const void* tgt_w1, const void* tgt_w2,
+                      const uint32_t* tgt_offset, const uint32_t* tgt_size, const uint32_t* tgt_res, const float* tgt_scale, const uint32_t* tgt_hashed,
+                      const float* tgt_roi_aabb, const float* tgt_model_aabb, const float* tgt_center,
+                      const float* pose, float power, float* sigma, float* w_src, float* w_tgt, float* sigma_src, float* sigma_tgt, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
