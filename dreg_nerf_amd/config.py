@@ -88,6 +88,19 @@ def config_parser(argv=None):
                    help="eval_nerf_regtr.py: per scene whose block checkpoints are on disk, mesh the registered pair as ONE density field (fused pair-density "
                         "kernel, DESIGN.md 3i; --mesh_resolution cells on the pair's longest axis, --mesh_level) under the predicted and the known pose: "
                         "merged_field_mesh_pred.ply, merged_field_mesh_gt.ply and merged_field_mesh.json (V, F, area, volume of both)")
+    p.add_argument("--register_scene", action="store_true",
+                   help="eval_nerf_regtr.py: after the normal pass, register every scene as a WHOLE: all ordered pairs of its blocks through the network, pose "
+                        "synchronisation into one pose per block (dreg_nerf_amd/pose_graph.py, DESIGN.md 3j), scene_metrics_{split}.json next to "
+                        "metrics_{split}.json, which is unchanged")
+    p.add_argument("--scene_robust", action="store_true",
+                   help="--register_scene: re-solve with the edges reweighted by their residuals, w0 / (1 + (theta / 2 deg)^2 + (|t| / 0.05)^2), ten rounds; "
+                        "neither scale is tuned (0.05 is round 0's voxel-average cell and ICP's default gate)")
+    p.add_argument("--synthetic_blocks", type=int, default=2,
+                   help="--synthetic with --register_scene / --render_scene: blocks per synthetic scene, 2 to 4 (another value ends the run before anything is evaluated)")
+    p.add_argument("--render_scene", action="store_true",
+                   help="eval_nerf_regtr.py: implies --register_scene (the whole registration runs and scene_metrics_{split}.json is written); then, per scene whose block checkpoints are on disk, render ALL its blocks as one scene (fused K-block "
+                        "renderer, DESIGN.md 3j) from every block's cameras under the ground-truth and the synchronised poses, and write PSNR / SSIM between the "
+                        "two to scene_render_metrics.json")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

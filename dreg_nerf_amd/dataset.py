@@ -307,15 +307,47 @@ class NeRFRegDataset:
         }
         return augment(data) if self.mode == "train" else data
 
+    def get_scene(self, index):
+        """ALL usable blocks of a scene, ordered by block id, never augmented, drawing from no RNG: a list of block dicts with `sparse`
+        (SparseBlock; dense datasets: `xyz_rgba` [1,7,Z,X,Y] and `mask`), `nerf_path`, `transform` [4,4], `block_id`, `scene`, `dataset`, `index`.
+        The pose that brings block i into the frame of block a is transform[a] @ inv(transform[i]) — get's `pose` with src = i, tgt = a."""
+        sm = self.meta[index]
+        scene = []
+        for k in sorted(sm["blocks"]):
+            b = sm["blocks"][k]
+            blk = {"nerf_path": os.path.join(b["dir"], "model.pth"), "transform": b["transform"].clone(), "block_id": k,
+                   "scene": sm["scene"], "dataset": sm["dataset"], "index": index}
+            if self.sparse:
+                sb = self._sparse_block(b["dir"])
+                blk["sparse"] = sb.to(self.device) if self.device is not None else sb
+            else:
+                blk["xyz_rgba"] = torch.load(os.path.join(b["dir"], "voxel_grid.pt")).permute(3, 2, 0, 1).unsqueeze(0).contiguous()
+                blk["mask"] = torch.load(os.path.join(b["dir"], "voxel_mask.pt"))
+            scene.append(blk)
+        return scene
+
 
 class SyntheticRegDataset:
-    """N shell-R scenes with a fixed, scene-dependent relative pose (stand-in for the external Objaverse data)."""
+    """N shell-R scenes with a fixed, scene-dependent relative pose (stand-in for the external Objaverse data).  n_blocks: blocks per scene for
+    get_scene (2 = the pair __getitem__ returns; the samples of __getitem__ do not depend on it)."""
 
-    def __init__(self, n_scenes: int, res: int = 128, split: str = "train"):
-        self.n, self.res, self.mode = n_scenes, res, split
+    def __init__(self, n_scenes: int, res: int = 128, split: str = "train", n_blocks: int = 2):
+        if not 2 <= n_blocks <= 4:
+            raise ValueError(f"SyntheticRegDataset: n_blocks = {n_blocks} (2 to 4)")
+        self.n, self.res, self.mode, self.n_blocks = n_scenes, res, split, n_blocks
 
     def __len__(self):
         return self.n
+
+    def get_scene(self, index):
+        """The scene's n_blocks blocks in NeRFRegDataset.get_scene's layout: blocks 0 and 1 are __getitem__'s source and target (transforms I and
+        the scene's pose), further blocks take further draws of the same generator."""
+        g = torch.Generator().manual_seed(1000 + index)
+        poses = [torch.eye(4)] + [_small_se3(0.25, g) for _ in range(self.n_blocks - 1)]
+        scene = synth.shell_scene(self.res, [2 * index + 1 + k for k in range(self.n_blocks)], poses)
+        for blk in scene:
+            blk.update({"scene": f"shell_{index:04d}", "dataset": "synthetic", "index": index})
+        return scene
 
     def __getitem__(self, index):
         g = torch.Generator().manual_seed(1000 + index)

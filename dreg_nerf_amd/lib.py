@@ -253,6 +253,8 @@ SIGNATURES = {
     "dreg_ngp_render": (I, [P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
     # render_pair.hip: n_rays, the source block's arguments, the target block's, then power, early_stop_eps, bkgd, the outputs, queue, stream
     "dreg_ngp_render_pair": (I, [ctypes.c_long] + ([P, P, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 4 + [P]) * 2 + [F, F, P] + [P] * 7),
+    # render_scene.hip: n_rays, n_blocks, a HOST array of SceneBlock, then power, early_stop_eps, bkgd, the outputs (weight_block [N,K]), queue, stream
+    "dreg_ngp_render_scene": (I, [ctypes.c_long, I, P, F, F, P] + [P] * 7),
     # render_train.hip
     "dreg_ngp_render_train": (I, [P, P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 6),
     "dreg_ngp_render_bwd_workspace_bytes": (Z, [ctypes.c_long]),
@@ -317,6 +319,7 @@ PROBE_SIGNATURES = {
     "dreg_render_set_waves": (None, [I]),
     "dreg_render_pair_set_waves": (None, [I]),
     "dreg_render_bwd_set_waves": (None, [I]),
+    "dreg_render_scene_set_waves": (None, [I]),
 }
 PROBE_LIB_PATH = os.path.join(_HERE, "libdreg_nerf_hip_probe.so")
 _probe_lib = None
@@ -326,6 +329,16 @@ class ExecOpts(ctypes.Structure):
     """dreg_exec_opts of include/dreg_nerf.h (creation options of one trunk executor)."""
     _fields_ = [(n, c_int) for n in ("sparse_grads", "bn_batch_tails", "fuse_stem", "sparse_stem", "fold_res_bn", "fold_splitk", "group_wgrad",
                                      "s2_accumulate", "fuse_bn_stats", "brick", "defer_head_pg", "persistent_deep", "guard", "pointwise_stream")] + [("reserved", c_int * 2)]
+
+
+SCENE_MAX_BLOCKS = 4
+
+
+class SceneBlock(ctypes.Structure):
+    """dreg_scene_block of include/dreg_nerf.h (one block's arguments of dreg_ngp_render_scene)."""
+    _fields_ = ([("origins", P), ("viewdirs", P), ("binary", P), ("rx", c_int), ("ry", c_int), ("rz", c_int), ("coarse_bits", P)] +
+                [(n, P) for n in ("table", "w1", "w2", "cw1", "cw2", "cw3", "offset", "size", "res", "scale", "hashed", "roi_aabb", "scene_aabb", "model_aabb")] +
+                [(n, c_float) for n in ("near_plane", "far_plane", "render_step_size", "alpha_thre")] + [("center", P)])
 
 
 def load_probe():

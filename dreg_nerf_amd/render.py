@@ -8,8 +8,12 @@ so parity is unpinned and that rule is the specification (CPU restatement: tests
 
 A registered pair of blocks as ONE scene goes through the fused two-block kernel of csrc/render_pair.hip (rays_to_block, render_pair_image,
 render_pair_views, and render_scene_merged for eval_nerf_regtr.py --render_merged; rule: DESIGN.md §3e, CPU restatement:
-tests/render_pair_restatement.py)."""
+tests/render_pair_restatement.py).
+
+Up to four registered blocks as ONE scene go through the fused K-block kernel of csrc/render_scene.hip (render_scene_image, render_blocks_views;
+rule: DESIGN.md §3j, CPU restatement: tests/render_scene_restatement.py); with two blocks it is the pair kernel bit for bit."""
 import collections
+import ctypes
 import math
 import os
 import shutil
@@ -241,6 +245,74 @@ def render_pair_views(blocks, pose: torch.Tensor, poses_c2w: torch.Tensor, K: to
         rgbs.append(rgb)
         depths.append(depth)
         shares.append(wsrc)
+    return rgbs, depths, shares
+
+
+# ---------------------------------------------------------------------------------------------------------------- K registered blocks as one scene
+def render_scene_image(blocks, rays, power: float = 4.0, render_bkgd: Optional[torch.Tensor] = None):
+    """K registered blocks (1 <= K <= 4) rendered as ONE scene by the fused K-block kernel (csrc/render_scene.hip).
+    blocks: a list of (field, grid, opts, center, pose) — opts as render_pair_image takes them (PAIR_OPTS), center the centroid of the block's
+    cameras in its own frame, pose = G_b ([3,4] or [4,4]) mapping the block's frame to the frame the rays are given in (rays_to_block brings
+    the rays into the block's frame), or None: the rays are passed to that block untouched (an identity pose would re-normalise the directions
+    in fp64 and change their bits).  rays: origins / viewdirs shaped [N,3] or [H,W,3] -> (colors [...,3], opacities [...,1], depths [...,1],
+    weight_block [...,K]: the part of the opacity each block's samples contributed, n_rendering_samples: int).  Inference only."""
+    blocks = list(blocks)
+    if not 1 <= len(blocks) <= L.SCENE_MAX_BLOCKS:
+        raise ValueError(f"render_scene_image: {len(blocks)} blocks (1 to {L.SCENE_MAX_BLOCKS} are rendered as one scene)")
+    if rays.origins.requires_grad or rays.viewdirs.requires_grad or any(b[0].training for b in blocks):
+        raise RuntimeError("render_scene_image: the fused renderer is inference only (no backward); call it under torch.no_grad() with eval-mode fields")
+    for f, _, opts, _, _ in blocks:
+        unknown = set(opts) - set(PAIR_OPTS)
+        if unknown:
+            raise TypeError(f"render_scene_image: unknown options {sorted(unknown)} (known: {PAIR_OPTS})")
+        if float(opts.get("cone_angle") or 0.0) != 0.0:
+            raise NotImplementedError("render_scene_image: cone_angle != 0 (unbounded marching) is not supported")
+        if opts.get("scene_aabb") is None or getattr(f, "unbounded", False):
+            raise NotImplementedError("render_scene_image: unbounded scenes (no scene aabb / contracted field) are not supported")
+    with torch.no_grad():
+        lib = L.load()
+        shp = rays.origins.shape
+        dev = blocks[0][0].mlp_base.params.device                         # (asked of the parameters: _prepared() of a host field would launch on host memory)
+        if any(b[0].mlp_base.params.device != dev for b in blocks[1:]):
+            raise ValueError("render_scene_image: all blocks must be on the same device")
+        keep = []
+        arr = (L.SceneBlock * len(blocks))()
+        names = [n for n, _ in L.SceneBlock._fields_]
+        for i, (f, g, opts, center, pose) in enumerate(blocks):
+            args = _pair_block_args(f, g, rays if pose is None else rays_to_block(rays, pose), opts, center, dev, keep)
+            for name, v in zip(names, args):
+                setattr(arr[i], name, ctypes.cast(v, ctypes.c_void_p) if isinstance(v, ctypes.Array) else v)
+        n = rays.origins.reshape(-1, 3).shape[0]
+        bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(v) for v in torch.as_tensor(render_bkgd).reshape(-1).tolist()]
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        opacity, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+        wblock = torch.empty(n, len(blocks), dtype=torch.float32, device=dev)
+        counters = torch.zeros(2, dtype=torch.int64, device=dev)          # surviving samples, then the ray queue
+        visibility.OVERRUN.check()
+        L.check(lib.dreg_ngp_render_scene(n, len(blocks), ctypes.cast(arr, ctypes.c_void_p), float(power), 1e-4, L.f3(bk),
+                                          L.ptr(rgb), L.ptr(opacity), L.ptr(depth), L.ptr(wblock), counters.data_ptr(), counters.data_ptr() + 8, L.stream()),
+                "dreg_ngp_render_scene")
+        visibility.OVERRUN.watch(counters[1:])
+        n_samples = int(counters[0].item())
+        visibility.OVERRUN.check(wait=True)
+        return rgb.view(*shp[:-1], 3), opacity.view(*shp[:-1], 1), depth.view(*shp[:-1], 1), wblock.view(*shp[:-1], len(blocks)), n_samples
+
+
+def render_blocks_views(blocks_loaded, poses, poses_c2w: torch.Tensor, K: torch.Tensor, W: int, H: int, bkgd=(1.0, 1.0, 1.0)):
+    """render_pair_views for a registered scene of K blocks: blocks_loaded = [(field, grid, meta)] per block, poses = [G_b] mapping each block's
+    frame to the common frame ([K,4,4] or a list), poses_c2w [N,4,4] cameras in the common frame.  The blocks' camera centroids come from
+    meta["camera_poses"].  Returns lists of device tensors: rgb [H,W,3], depth [H,W,1], weight_block [H,W,K].
+    (Not named render_scene_views: that is the --render_views writer of a pair, below.)"""
+    dev = blocks_loaded[0][0]._prepared()[0].device
+    bk = torch.tensor(bkgd, dtype=torch.float32)
+    blocks = [(f, g, block_pair_opts(m), torch.as_tensor(m["camera_poses"]).float()[:, :3, 3].mean(0).cpu(), G)
+              for (f, g, m), G in zip(blocks_loaded, poses)]
+    rgbs, depths, shares = [], [], []
+    for c2w in poses_c2w:
+        rgb, _, depth, wb, _ = render_scene_image(blocks, pixel_rays(c2w.to(dev), K, W, H), render_bkgd=bk)
+        rgbs.append(rgb)
+        depths.append(depth)
+        shares.append(wb)
     return rgbs, depths, shares
 
 

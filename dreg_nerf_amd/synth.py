@@ -68,6 +68,23 @@ def shell_pair(res: int, seed_src: int = 1, seed_tgt: int = 2, pose: torch.Tenso
     }
 
 
+def shell_scene(res: int, seeds, poses) -> list:
+    """shell_pair generalised to K blocks: one scene in the layout NeRFRegDataset.get_scene returns — a list of K block dicts with xyz_rgba
+    [1,7,Z,X,Y], mask int64, transform [4,4], nerf_path and block_id, ordered by id.  poses[i] ([4,4]) is block i's transform in get_scene's
+    sense: it is applied to the stored xyz, and the ground truth that brings block i into the anchor's frame is
+    G_i = poses[anchor] @ inv(poses[i]) (shell_pair(res, a, b, pose) is the pair of transforms (I, pose))."""
+    seeds, poses = list(seeds), list(poses)
+    if len(seeds) != len(poses) or not seeds:
+        raise ValueError(f"shell_scene: {len(seeds)} seeds for {len(poses)} poses")
+    r0, r1 = shell_radii(res)
+    scene = []
+    for k, (seed, pose) in enumerate(zip(seeds, poses)):
+        pose = torch.as_tensor(pose, dtype=torch.float32)
+        g, m = shell_grid(res, seed, r0, r1, pose=pose)
+        scene.append({"xyz_rgba": g.permute(3, 2, 0, 1).unsqueeze(0).contiguous(), "mask": m, "transform": pose.clone(), "nerf_path": "", "block_id": k})
+    return scene
+
+
 def synthetic_overlap_gt(kp: torch.Tensor, nl: int = 6) -> torch.Tensor:
     """Deterministic stand-in for the ray-marched visibility labels: a half-space test
     1[x + 0.31 y - 0.17 z > 0.0123] broadcast to [nl, N, 1].  (A radial threshold inside the shell would

@@ -4,7 +4,9 @@
 both NeRF blocks under the ground-truth, predicted and no alignment, :113-172 / :345-369; with --render_merged, which the reference lacks,
 both blocks rendered as one scene under the ground-truth and the predicted pose and merged_metrics.json; with --merged_mesh the two
 blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / merged_mesh_gt.ply; with --merged_mesh_field the pair meshed as ONE density field, one closed surface per pose,
-merged_field_mesh_pred.ply / merged_field_mesh_gt.ply / merged_field_mesh.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+merged_field_mesh_pred.ply / merged_field_mesh_gt.ply / merged_field_mesh.json; with --register_scene every scene registered as a
+whole — all ordered pairs of its blocks, pose synchronisation, scene_metrics_<split>.json — and with --render_scene all its blocks rendered as one
+scene under the ground-truth and the synchronised poses): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -88,6 +90,37 @@ def write_ransac(d, split, rows, ransac_rows, ransac_refined_rows=None, log=prin
     return out
 
 
+def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer=None, metrics=None, log=print):
+    """--register_scene [--scene_robust] [--render_scene]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
+    {scene: row of scene_metrics_{split}.json}.  Runs after the normal pass; get_scene, the forward calls and the synchronisation draw from no
+    random stream.  pair_fn / renderer / metrics are scene_reg's injection points (tests)."""
+    from dreg_nerf_amd import scene_reg
+    rows = {}
+    for i in ES.my_scenes(len(ds), rank, world):
+        scene = ds.get_scene(i)
+        name = str(scene[0].get("scene", i))
+        res = scene_reg.register_scene(model, scene, robust=cfg.scene_robust, pair_fn=pair_fn, eval_batch=max(cfg.eval_batch, 1), device=dev)
+        rows[name] = scene_reg.scene_row(res, scene)
+        if cfg.render_scene:
+            paths = [b.get("nerf_path", "") for b in scene]
+            if renderer is not None or all(p and os.path.exists(p) for p in paths):
+                scene_dir = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", name)
+                mm = scene_reg.render_registered_scene(scene_dir, scene, scene_reg.ground_truth(scene), res["G"], cfg.dataset, dev, renderer=renderer, metrics=metrics)
+                log(f"{name}: scene render of {len(scene)} blocks, aligned vs gt PSNR {mm['psnr_mean']:.2f} dB, SSIM {mm['ssim_mean']:.4f}", flush=True)
+            else:
+                log(f"{name}: no NeRF blocks on disk, scene not rendered", flush=True)
+    return rows
+
+
+def write_scenes(d, split, scene_rows, log=print):
+    """scene_metrics_{split}.json and the synchronised poses' RRE / RTE beside the direct edges'."""
+    from dreg_nerf_amd import scene_reg
+    out = scene_reg.write_scene_metrics(os.path.join(d, f"scene_metrics_{split}.json"), scene_rows)
+    log(f"scene registration, {len(scene_rows)} scenes: synchronised R_mean {out['R_mean']:.3f} deg, t_mean {out['t_mean']:.4f} | direct edges R_mean "
+        f"{out['R_mean_direct']:.3f} deg, t_mean {out['t_mean_direct']:.4f} -> {d}/scene_metrics_{split}.json", flush=True)
+    return out
+
+
 def init_distributed(local_rank: int):
     """One process per GPU under torch.distributed.run: RCCL ('nccl' on ROCm).  DREG_EVAL_BACKEND=gloo with DREG_EVAL_ONE_GPU=1 is the test hook bench.py
     has too — several ranks on the one GPU of a test box exercise the sharding and the gather (tests/test_hip_eval_pipeline.py); never a measurement."""
@@ -104,6 +137,10 @@ def init_distributed(local_rank: int):
 
 def main():
     cfg = config_parser()
+    if cfg.render_scene:
+        cfg.register_scene = True    # the scene render needs the synchronised poses: --render_scene implies --register_scene (and its scene_metrics file)
+    if cfg.register_scene and cfg.synthetic > 0 and not 2 <= cfg.synthetic_blocks <= 4:
+        raise SystemExit(f"--synthetic_blocks {cfg.synthetic_blocks}: a synthetic scene has 2 to 4 blocks")      # before the normal pass, not after it
     import random
     import numpy as np
     random.seed(cfg.seed)            # setup_seed(config.seed) of the reference (eval_nerf_regtr.py:462, conerf/utils/utils.py:21-26): the block order of
@@ -219,7 +256,14 @@ def main():
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])
                 fgr_rows[data["scene"]] = {"R_mean": float(e["R_error_mean"]), "t_mean": float(e["t_error_mean"]),
                                            "R_med": float(e["R_error_med"]), "t_med": float(e["t_error_med"]), "time": sec}
+    scene_rows = {}
+    if cfg.register_scene:   # whole scenes, after the normal pass and apart from it: nothing above reads what this computes
+        sds = SyntheticRegDataset(cfg.synthetic, cfg.synthetic_res, split, n_blocks=cfg.synthetic_blocks) if cfg.synthetic > 0 else ds
+        with torch.no_grad():
+            scene_rows = register_scenes(cfg, sds, model, dev, rank, world)
     rows, fgr_rows, refined_rows = ES.gather_rows(rows, world), ES.gather_rows(fgr_rows, world), ES.gather_rows(refined_rows, world)
+    if cfg.register_scene:
+        scene_rows = ES.gather_rows(scene_rows, world)
     if cfg.ransac_pose:
         ransac_rows, ransac_refined_rows = ES.gather_rows(ransac_rows, world), ES.gather_rows(ransac_refined_rows, world)
     if rank == 0:
@@ -238,6 +282,8 @@ def main():
             write_refined(d, split, rows, refined_rows)
         if ransac_rows:
             write_ransac(d, split, rows, ransac_rows, ransac_refined_rows)
+        if scene_rows:
+            write_scenes(d, split, scene_rows)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -790,6 +790,35 @@ int dreg_ngp_render_pair(long n_rays,
                          float power, float early_stop_eps, const float* bkgd,
                          float* rgb, float* opacity, float* depth, float* weight_src, unsigned long long* n_samples, void* queue, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- a registered scene of K blocks as one scene
+ * (csrc/render_scene.hip; rule: DESIGN.md §3j) dreg_ngp_render_pair generalised to 1 <= n_blocks <= DREG_SCENE_MAX_BLOCKS blocks: every ray is
+ * marched through all blocks at once, each on its own lattice, and the samples are composited in depth order (the lowest block index first on a
+ * tie); a sample that other blocks cover as well is weighted by inverse distance to the blocks' camera centroids, the weights of the covering
+ * blocks summing to 1.  dreg_scene_block holds ONE block's arguments of dreg_ngp_render_pair: origins / viewdirs in that block's frame (device),
+ * the grid, coarse bits and the six weight / table pointers (device), the level arrays, the three aabbs and center as HOST pointers.  `blocks` is
+ * a HOST array of n_blocks of them, read before the call returns.  Outputs as dreg_ngp_render plus weight_block fp32 [n_rays, n_blocks], the
+ * part of the opacity each block's samples contributed.  n_samples and queue are zeroed by the caller on `stream`; bit 63 of the queue word is
+ * set if the launch reached its pass bound.  Never allocates.  On any invalid argument (n_blocks out of range, a null in a block, ...) nothing
+ * is launched and DREG_EINVAL is returned.  With n_blocks = 2 the results equal dreg_ngp_render_pair's bit for bit (weight_block[:,0] =
+ * weight_src), with n_blocks = 1 dreg_ngp_render's. */
+#define DREG_SCENE_MAX_BLOCKS 4
+typedef struct dreg_scene_block {
+    const float* origins;
+    const float* viewdirs;
+    const uint8_t* binary;
+    int rx, ry, rz;
+    const uint32_t* coarse_bits;
+    const void *table, *w1, *w2, *cw1, *cw2, *cw3;
+    const uint32_t *offset, *size, *res;
+    const float* scale;
+    const uint32_t* hashed;
+    const float *roi_aabb, *scene_aabb, *model_aabb;
+    float near_plane, far_plane, render_step_size, alpha_thre;
+    const float* center;
+} dreg_scene_block;
+int dreg_ngp_render_scene(long n_rays, int n_blocks, const dreg_scene_block* blocks, float power, float early_stop_eps, const float* bkgd,
+                          float* rgb, float* opacity, float* depth, float* weight_block, unsigned long long* n_samples, void* queue, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- training of a NeRF block
  * (csrc/render.hip, csrc/render_train.hip; rule: DESIGN.md §3c).
  * dreg_ngp_render_train = dreg_ngp_render with stratified marching: ray i starts at t_min + jitter[i] * render_step_size, jitter fp32 [n_rays]

@@ -49,6 +49,7 @@ int dreg_visibility_set_pass_bound(long passes);   /* test hook: passes of the p
 void dreg_visibility_set_waves(int n);               /* one-wave workgroups of dreg_surface_visibility_queue's persistent launch (default 4096 = 256 CUs x 16) */
 void dreg_render_set_waves(int n);                   /* one-wave workgroups of dreg_ngp_render's persistent launch (default 2048 = 256 CUs x 8); same results at every width */
 void dreg_render_pair_set_waves(int n);              /* one-wave workgroups of dreg_ngp_render_pair's persistent launch (default 2048); same results at every width */
+void dreg_render_scene_set_waves(int n);             /* one-wave workgroups of dreg_ngp_render_scene's persistent launch (default 2048); same results at every width */
 void dreg_render_bwd_set_waves(int n);               /* one-wave workgroups of dreg_ngp_render_bwd's persistent launch (default 2048); same gradients at every width */
 void dreg_conv_set_narrow_small(int on);              /* 1 (default): launches of < 224 128 x 128 tiles use 128 x 64 tiles (twice the workgroups) */
 
