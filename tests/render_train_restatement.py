@@ -80,15 +80,17 @@ def fp32_backward():
         N.f16 = saved
 
 
-def render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd=None):
+def render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd=None, dtype=torch.float32):
     """The training forward over the oracle's NGP network (base = mlp_base.params, color = color_mlp.params, fp32, may require grad):
     (rgb [R,3], opacity [R], depth [R], survivors [R,S]).  sigma = trunc_exp(h0 - 1) whose backward is exp(min(h0 - 1, 15)).  Forward values
-    are the oracle's (fp16 roundings); gradients flow in fp32."""
+    are the oracle's (fp16 roundings); gradients flow in fp32.  dtype = torch.float64: the sums between the fp16 roundings, the compositing and
+    the gradients in fp64 (the march and the cell of every sample stay the fp32 ones): the second form of this reference, whose distance from
+    the first says what the reference itself can hold (tests/test_render_bwd_host.py, profiles/render_bwd_fp64_ratios.txt)."""
     with fp32_backward():
-        return _render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd)
+        return _render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd, dtype)
 
 
-def _render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd):
+def _render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, dt, jitter, bkgd, dtype=torch.float32):
     o, d = o.float().cpu(), d.float().cpu()
     roi_aabb, scene_aabb = torch.as_tensor(roi_aabb, dtype=torch.float32), torch.as_tensor(scene_aabb, dtype=torch.float32)
     model_aabb = torch.as_tensor(model_aabb, dtype=torch.float32)
@@ -100,14 +102,14 @@ def _render_train(base, color, model_aabb, o, d, binary, roi_aabb, scene_aabb, d
     lo, hi = model_aabb[:3], model_aabb[3:]
     u = (x - lo) / (hi - lo)
     selector = ((u > 0.0) & (u < 1.0)).all(dim=-1)
-    w1, w2, table = N.split_density_params(base)
-    enc = N.hash_encode(u, N.f16(table))
+    w1, w2, table = N.split_density_params(base.to(dtype))
+    enc = N.hash_encode(u, N.f16(table)).to(dtype)
     h = N.f16(torch.relu(enc @ N.f16(w1).T))
     raw = N.f16(h @ N.f16(w2).T)
-    s = _TruncExp.apply(raw[:, 0] - 1.0) * selector.float()
-    c = N.query_rgb(d[idx[:, 0]], raw, color)
-    sigma = torch.zeros(R, S).index_put((idx[:, 0], idx[:, 1]), s)
-    rgb_s = torch.zeros(R, S, 3).index_put((idx[:, 0], idx[:, 1]), c)
+    s = _TruncExp.apply(raw[:, 0] - 1.0) * selector.to(dtype)
+    c = N.query_rgb(d[idx[:, 0]], raw, color.to(dtype))
+    sigma = torch.zeros(R, S, dtype=dtype).index_put((idx[:, 0], idx[:, 1]), s)
+    rgb_s = torch.zeros(R, S, 3, dtype=dtype).index_put((idx[:, 0], idx[:, 1]), c)
     out = composite(sigma, rgb_s, occ, tm, dt, bkgd)
     _LAST_SAMPLES.update(u=u.detach(), ray=idx[:, 0], surv=out[3][idx[:, 0], idx[:, 1]])
     return out

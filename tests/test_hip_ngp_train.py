@@ -67,23 +67,58 @@ def test_train_forward_zero_jitter_equals_render_bitwise():
     assert out[3] == ref[3] > 0
 
 
-def _cpu_reference(f, g, rays, jitter, dt, bkgd, g_rgb, mask):
+def _cpu_reference(f, g, rays, jitter, dt, bkgd, g_rgb, mask, model=AABB, dtype=torch.float32):
     import render_train_restatement as RT
     base = f.mlp_base.params.detach().cpu().clone().requires_grad_(True)
     color = f.color_mlp.params.detach().cpu().clone().requires_grad_(True)
-    rgb, opac, depth, surv = RT.render_train(base, color, AABB, rays.origins, rays.viewdirs, g.binary.cpu(), AABB, AABB, dt, jitter.cpu(), bkgd)
-    (rgb * (g_rgb * mask[:, None])).sum().backward()
-    return rgb.detach(), opac.detach(), base.grad, color.grad, surv
+    rgb, opac, depth, surv = RT.render_train(base, color, model, rays.origins, rays.viewdirs, g.binary.cpu(), AABB, AABB, dt, jitter.cpu(), bkgd, dtype=dtype)
+    (rgb * (g_rgb * mask[:, None]).to(dtype)).sum().backward()
+    return rgb.detach().float(), opac.detach().float(), base.grad, color.grad, surv
 
 
-def test_backward_matches_cpu_autograd():
+# model aabb of the second parametrisation: strictly inside the scene aabb and cutting the occupied ball (radius 0.8), so kept samples outside the
+# model exist (sigma = 0 there: they survive, weigh nothing, and dL/dh0 is forced to 0)
+MODEL_INSIDE = [-0.6, -0.55, -0.65, 0.55, 0.6, 0.5]
+
+
+def blocks_of(gb, gc, touched):
+    """The blocks the two criteria are applied to, one by one: name -> index into (grad of mlp_base.params | grad of color_mlp.params)."""
+    from oracle import ngp_oracle as N
+    out = {"density W1": (0, slice(0, 2048)), "density W2": (0, slice(2048, 3072)), "colour W2": (1, slice(2048, 6144)),
+           "colour W3 (rgb rows)": (1, slice(6144, 6144 + 192))}
+    cols = torch.arange(2048).reshape(64, 32)
+    out["colour W1 sh columns 0..15"] = (1, cols[:, :16].reshape(-1))
+    out["colour W1 feature columns 16..30"] = (1, cols[:, 16:31].reshape(-1))
+    out["colour W1 column 31"] = (1, cols[:, 31].reshape(-1))
+    for l, row in enumerate(N.level_table()[0]):
+        idx = torch.nonzero(touched[2 * row["offset"]:2 * (row["offset"] + row["size"])]).reshape(-1) + 2 * row["offset"] + 3072
+        out[f"hash table level {l} (touched)"] = (0, idx)
+    return out
+
+
+def cos_rel(a, b):
+    cos = torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), b.double().reshape(1, -1)).item()
+    return cos, ((a.double() - b.double()).norm() / b.double().norm()).item()
+
+
+@pytest.mark.parametrize("model", [AABB, MODEL_INSIDE], ids=["model_is_scene", "model_inside_scene"])
+def test_backward_matches_cpu_autograd(model):
     """GPU gradients against autograd through the restatement over oracle.ngp_oracle, on the rays whose forward agrees (>= 99 %).
     Tolerances: the kernel and the oracle share the fp16 forward (table, weights, activations rounded to fp16, fp32 sums); they differ in the
-    order of the fp32 sums and in the backward's own arithmetic (fp32 on the GPU, fp32 autograd through fp16-rounded values on the CPU), so the
-    MLP gradients must agree to cosine >= 0.999 and relative L2 <= 2e-2, the table gradient on touched entries to relative L2 <= 2e-2."""
+    order of the fp32 sums and in the backward's own arithmetic (fp32 on the GPU, fp32 autograd through fp16-rounded values on the CPU), so
+    cosine >= 0.999 and relative L2 <= 2e-2 must hold BLOCK BY BLOCK: each of the five matrices, colour W1 split into its SH columns 0..15,
+    its feature columns 16..30 and the constant-1 column 31, and the hash table level by level over the touched entries of that level.
+    (tests/test_hip_render_bwd_fp64.py holds the same kernel to fp64 element by element on a flat field; this is the general, non-flat field.)
+    Every block's reference holds these figures on its own: the distance between the restatement run with an fp32 forward and with an fp64
+    forward (render_train(dtype=torch.float64), both with the fp16 straight-through roundings; measured and asserted on the CPU on these very rays by
+    tests/test_render_bwd_host.py::test_general_field_reference_holds_its_figures_block_by_block) is at
+    most 1.05e-3 relative L2 (hash table level 8, model inside the scene; 2.9e-4 with model == scene) and 1 - cosine <= 5.5e-7, so no block
+    needs a margin of its own; the measured distances are in profiles/render_bwd_fp64_ratios.txt."""
     dev = _dev()
     from dreg_nerf_amd import ngp_train, render
     f, g = _block(dev, seed=3)
+    with torch.no_grad():
+        f.aabb.copy_(torch.tensor(model, dtype=torch.float32))
     n = 300
     rays = _rays(n, seed=4)
     dt = 0.02
@@ -93,7 +128,7 @@ def test_backward_matches_cpu_autograd():
     f.train()
     rays_d = render.Rays(rays.origins.to(dev), rays.viewdirs.to(dev))
     rgb, opac, _, ns = ngp_train.render_image_train(f, g, rays_d, AABB, dt, bk, jitter=jitter.to(dev))
-    rgb_c, opac_c, _, _, surv_c = _cpu_reference(f, g, rays, jitter, dt, bk, torch.zeros(n, 3), torch.zeros(n))
+    rgb_c, opac_c, _, _, surv_c = _cpu_reference(f, g, rays, jitter, dt, bk, torch.zeros(n, 3), torch.zeros(n), model)
     # survivors per ray on the GPU: one launch per ray (the kernel reports the total only)
     with torch.no_grad():
         per_ray = torch.tensor([ngp_train.render_image_train(f, g, render.Rays(rays_d.origins[i:i + 1], rays_d.viewdirs[i:i + 1]), AABB, dt, bk,
@@ -106,22 +141,20 @@ def test_backward_matches_cpu_autograd():
     f.color_mlp.params.grad = None
     (rgb * (g_rgb.to(dev) * mask.to(dev)[:, None])).sum().backward()
     gb, gc = f.mlp_base.params.grad.cpu(), f.color_mlp.params.grad.cpu()
-    _, _, rb, rc, _ = _cpu_reference(f, g, rays, jitter, dt, bk, g_rgb, mask)
-
-    def close(a, b, what, cos_min=0.999, rel=2e-2):
-        cos = torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), b.double().reshape(1, -1)).item()
-        r = ((a.double() - b.double()).norm() / b.double().norm()).item()
-        assert cos >= cos_min and r <= rel, f"{what}: cosine {cos:.5f}, rel L2 {r:.3e}"
-
-    close(gb[:2048], rb[:2048], "density W1")
-    close(gb[2048:3072], rb[2048:3072], "density W2")
-    close(gc[:2048], rc[:2048], "colour W1")
-    close(gc[2048:6144], rc[2048:6144], "colour W2")
-    close(gc[6144:6144 + 192], rc[6144:6144 + 192], "colour W3 (rgb rows)")
-    assert torch.count_nonzero(gc[6144 + 192:]) == 0
+    _, _, rb, rc, _ = _cpu_reference(f, g, rays, jitter, dt, bk, g_rgb, mask, model)
     import render_train_restatement as RT
     touched = RT.reached_entries(agree)
-    close(gb[3072:][touched], rb[3072:][touched], "hash table (touched)")
+    if model is MODEL_INSIDE:
+        outside = ~((RT._LAST_SAMPLES["u"] > 0) & (RT._LAST_SAMPLES["u"] < 1)).all(-1)
+        assert int((outside & RT._LAST_SAMPLES["surv"]).sum()) > 100
+    failed = []
+    for what, (which, idx) in blocks_of(gb, gc, touched).items():
+        cos, r = cos_rel((gb, gc)[which][idx], (rb, rc)[which][idx])
+        print(f"BLOCK {what}: cosine {cos:.6f}, rel L2 {r:.3e}")
+        if not (cos >= 0.999 and r <= 2e-2):
+            failed.append(f"{what}: cosine {cos:.5f}, rel L2 {r:.3e}")
+    assert not failed, failed
+    assert torch.count_nonzero(gc[6144 + 192:]) == 0
     # untouched entries are 0, save corners whose sample position differs from the CPU's by an ulp and falls across a cell face with a
     # trilinear weight below ~1e-5 (measured: 26 of 2.9 M entries, <= 2.5e-6 of the largest gradient)
     stray = (gb[3072:] != 0) & ~touched
