@@ -101,6 +101,10 @@ def config_parser(argv=None):
                    help="eval_nerf_regtr.py: implies --register_scene (the whole registration runs and scene_metrics_{split}.json is written); then, per scene whose block checkpoints are on disk, render ALL its blocks as one scene (fused K-block "
                         "renderer, DESIGN.md 3j) from every block's cameras under the ground-truth and the synchronised poses, and write PSNR / SSIM between the "
                         "two to scene_render_metrics.json")
+    p.add_argument("--scene_mesh_field", action="store_true",
+                   help="eval_nerf_regtr.py: implies --register_scene; then, per scene whose block checkpoints are on disk, mesh ALL its blocks as ONE density field "
+                        "(fused K-block density kernel, DESIGN.md 3k; --mesh_resolution cells on the scene's longest axis, --mesh_level) under the ground-truth "
+                        "and the synchronised poses: scene_field_mesh_gt.ply, scene_field_mesh_aligned.ply and scene_field_mesh.json (K; V, F, area, volume of both)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

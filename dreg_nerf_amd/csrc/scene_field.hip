@@ -1,0 +1,247 @@
+// The density of a REGISTERED SCENE of K NeRF blocks (1 <= K <= DREG_SCENE_MAX_BLOCKS = 4) as one scalar field, gfx950: the field the K-block
+// renderer (render_scene.hip) composites, evaluated at points or over a lattice in ONE kernel, so that the mesher
+// (marching_cubes.hip) extracts the surface of the whole registered scene (the K-block form of pair_field.hip; rule: DESIGN.md §3k, CPU
+// restatement: tests/scene_field_restatement.py).
+//
+// Frames.  The field lives in the SCENE frame (the anchor's frame of pose_graph.synchronize).  Block b has a pose G_b = [R_b|t_b] mapping its frame
+// to the scene frame, rounded to fp32 once by the host (12 floats), or no pose.  For a point x (fp32):
+//   with a pose     d = x - t_b, x_b[k] = (R_b[0][k] d[0] + R_b[1][k] d[1]) + R_b[2][k] d[2]    (fp32, this order, no contraction: pair_field.hip's
+//                   expression, the same bits as torch fp32 elementwise ops)
+//   without         x_b = x, the same bits
+// Own coverage     m_b(x_b): pair_field_covered's rule (inside the roi, the cell clamp(floor(u res), 0, res - 1) set)
+// Densities        sigma_b = block b's density at x_b, the dense query's bit for bit (ngp_unit_cube, ngp_level_features, ngp_density_mlp,
+//                  __expf(h0 - 1) times the strictly-inside flag)
+// Weight           render_scene.hip's overlap weight, operation for operation: delta_b = |x_b - c_b|^2 + 1e-12f (the squares summed from 0.f in axis
+//                  order), C_b = the OTHER blocks with m = 1;  m_b = 0: omega_b = 0;  |C_b| = 0: omega_b = 1;
+//                  |C_b| = 1: with lo / hi the lower / higher index of the two, omega_lo = 1 / (1 + __expf(p/2 __logf(delta_lo / delta_hi))),
+//                             omega_hi = 1 - omega_lo;
+//                  |C_b| >= 2: omega_b = 1 / (1 + sum over b' in C_b, ascending, of __expf(p/2 __logf(delta_b / delta_b')))
+// Scene density    sigma = ((p_0 + p_1) + p_2) + p_3 with p_b = fl(omega_b sigma_b); absent or uncovered blocks contribute + 0.f (every term is >= 0:
+//                  adding + 0.f changes no bit).  With K = 2 and blocks [(src, P), (tgt, none)] every output is dreg_pair_density's, bit for bit.
+//
+// One lane = one point, 64 points per wave, one-wave workgroups that stride over the 64-point chunks; points form and lattice form as
+// pair_density_kernel.  Per chunk: the positions and all K coverages (a bit mask per lane) and distances, then the weights, then block b's
+// density phase (its MFMA operands, the 16-level gather, the MLP through the one 64 x 64 fp16 LDS tile) only when some lane has m_b set.  Every
+// loop over the block index that reads a block is ONE non-unrolled body that reads the block and its pose from the kernel-argument segment, for
+// the reason render_pair.hip's header gives.  Nothing per-lane is indexed by a run-time block index (that would go to scratch): delta_b, sigma_b
+// and omega_b sit in K named registers, written by select inside unrolled loops, and x_b is recomputed in the phase from the same operands (the
+// same bits).  No atomics, no process-global state; a point's result depends on nothing but the point.  As built: DESIGN.md §3k.
+#include "march.h"
+#include "../../include/dreg_nerf.h"   // dreg_field_block, DREG_SCENE_MAX_BLOCKS and the signature check of the entry point defined here
+
+#define FIELD_MAXB DREG_SCENE_MAX_BLOCKS
+
+struct SceneFieldBlock : MarchBlock {
+    float center[3];            // centroid of the block's cameras, in the block's frame
+    float R[9], t[3];           // the pose rounded to fp32: R row-major, then t (block -> scene); unused without a pose
+    int has_pose;
+};
+
+struct SceneFieldArgs {
+    SceneFieldBlock b[FIELD_MAXB];      // the first K are filled, the rest zero
+    int K;
+    float half_power;
+    const float* x;             // points form: [n,3]; null: lattice form
+    float origin[3], spacing[3];
+    int nx, ny;                 // lattice form: nodes per x row, rows per z plane
+    int chunks_per_row;         // lattice form: ceil(nx / 64)
+    long n;                     // points, or nodes (nx ny nz)
+    long chunks;                // 64-point chunks of the launch
+    float *sigma, *weight_block, *sigma_block;      // the last two may be null; [n,K]
+};
+static_assert(sizeof(SceneFieldArgs) <= 4096, "the blocks are read from the kernel-argument segment");
+
+static constexpr long SCENE_FIELD_WAVES = 16384;    // one-wave workgroups of the launch at most (pair_density_kernel's width)
+
+// the scene-frame point x in block b's frame
+__device__ __forceinline__ void scene_field_to_block(const SceneFieldBlock& b, const float (&x)[3], float (&xb)[3])
+{
+    if (b.has_pose) {
+        const float d[3] = {x[0] - b.t[0], x[1] - b.t[1], x[2] - b.t[2]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xb[k] = (b.R[k] * d[0] + b.R[3 + k] * d[1]) + b.R[6 + k] * d[2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xb[k] = x[k];
+    }
+}
+
+// whether block b's own occupancy grid covers the point x of its frame (pair_field_covered of pair_field.hip, restated: that file is not edited)
+__device__ __forceinline__ bool scene_field_covered(const MarchBlock& b, const float (&x)[3])
+{
+    const int rdim[3] = {b.rx, b.ry, b.rz};
+    float u[3];
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { u[k] = (x[k] - b.roi[k]) / (b.roi[3 + k] - b.roi[k]); inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
+    if (!inside) return false;
+    int ci[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)rdim[k]), 0), rdim[k] - 1);
+    return b.binary[((long)ci[0] * b.ry + ci[1]) * b.rz + ci[2]] != 0;
+}
+
+// (the pair kernel's residency: four waves per SIMD, what the 9.25 KB of LDS per wave admit)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void scene_density_kernel(SceneFieldArgs a)
+{
+    // ONE 64 x 64 fp16 tile per wave, the encoded input in its first rows until the first layer has read it (pair_density_kernel's layout)
+    __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];
+    __shared__ float sOut[64];
+    char* sX = sH;
+    const int lane = threadIdx.x;
+    const int fr = lane & 15, kg = lane >> 4;
+    const int K = a.K;
+    for (long chunk = blockIdx.x; chunk < a.chunks; chunk += gridDim.x) {
+        // ---- the lane's point in the scene frame and where its results go
+        long idx;
+        bool valid;
+        float xw[3] = {0.f, 0.f, 0.f};
+        if (a.x != nullptr) {
+            idx = chunk * 64 + lane;
+            valid = idx < a.n;
+            if (valid) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) xw[k] = a.x[idx * 3 + k];
+            }
+        } else {
+            const long row = chunk / a.chunks_per_row;                    // iy + ny * iz
+            const int ix = (int)(chunk - row * a.chunks_per_row) * 64 + lane;
+            const int iz = (int)(row / a.ny), iy = (int)(row - (long)iz * a.ny);
+            valid = ix < a.nx;
+            idx = row * a.nx + ix;
+            const int ic[3] = {ix, iy, iz};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) xw[k] = a.origin[k] + (float)ic[k] * a.spacing[k];
+        }
+        // ---- every block's own coverage (a bit per block) and the point's squared distance to the block's camera centroid
+        unsigned mask = 0;
+        float del[FIELD_MAXB] = {1.f, 1.f, 1.f, 1.f};
+#pragma unroll 1
+        for (int q = 0; q < K; ++q) {
+            const SceneFieldBlock& b = a.b[q];
+            float xb[3];
+            scene_field_to_block(b, xw, xb);
+            const bool m = valid && scene_field_covered(b, xb);
+            float d = 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { const float e = xb[k] - b.center[k]; d += e * e; }
+            d += 1e-12f;
+            if (m) mask |= 1u << q;
+#pragma unroll
+            for (int j = 0; j < FIELD_MAXB; ++j) del[j] = (j == q) ? d : del[j];
+        }
+        // ---- the overlap weights (render_scene.hip's arithmetic; the distances are in registers: nothing is read per block)
+        float om[FIELD_MAXB];
+#pragma unroll
+        for (int j = 0; j < FIELD_MAXB; ++j) {
+            float w = 0.f;
+            if ((mask >> j) & 1u) {
+                const unsigned others = mask & ~(1u << j);
+                w = 1.f;
+                if (others != 0) {
+                    if (__popc(others) == 1 && others < (1u << j)) {            // the one other block has the lower index: the pair's omega_hi = 1 - omega_lo
+                        float d_lo = 1.f;
+#pragma unroll
+                        for (int i = 0; i < FIELD_MAXB; ++i) d_lo = ((others >> i) & 1u) ? del[i] : d_lo;
+                        w = 1.f - 1.f / (1.f + __expf(a.half_power * __logf(d_lo / del[j])));
+                    } else {
+                        float sum = 0.f;
+#pragma unroll
+                        for (int i = 0; i < FIELD_MAXB; ++i)
+                            if (i != j && ((others >> i) & 1u)) sum += __expf(a.half_power * __logf(del[j] / del[i]));
+                        w = 1.f / (1.f + sum);
+                    }
+                }
+            }
+            om[j] = w;
+        }
+        // ---- each block's density where that block covers the point; one body serves all blocks (the block's arguments are read per phase)
+        float sig[FIELD_MAXB] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int q = 0; q < K; ++q) {
+            const bool have = (mask >> q) & 1u;
+            if (!__any(have)) continue;
+            const SceneFieldBlock& b = a.b[q];
+            float xb[3], u[3];
+            scene_field_to_block(b, xw, xb);
+            const bool inside_m = ngp_unit_cube(xb, b.model, b.model + 3, 0, u);
+#pragma unroll 1
+            for (int l = 0; l < 16; ++l) {
+                float f0 = 0.f, f1 = 0.f;
+                if (have) ngp_level_features(b.table, b.lv, l, u, f0, f1);
+                _Float16* xr = reinterpret_cast<_Float16*>(sX + lane * NGP_XRS);
+                xr[2 * l] = (_Float16)f0; xr[2 * l + 1] = (_Float16)f1;
+            }
+            NgpDensityW dw;
+            ngp_load_density_w(dw, b.w1, b.w2, lane);
+            ngp_density_mlp(dw, sX, sH, lane, [&](int rb, const f32x4_t& ov) {      // ov[r] = output fr of point rb*16 + kg*4 + r
+                if (fr == 0) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sOut[rb * 16 + kg * 4 + r] = (float)(_Float16)ov[r];
+                }
+            });
+            wave_sync();
+            const float s = __expf(sOut[lane] - 1.f) * (inside_m ? 1.f : 0.f);          // the dense query's density (ngp_density_kernel)
+#pragma unroll
+            for (int j = 0; j < FIELD_MAXB; ++j) sig[j] = (j == q && have) ? s : sig[j];
+            wave_sync();                                                             // sOut and the tile are rewritten by the next phase
+        }
+        if (valid) {
+            a.sigma[idx] = ((om[0] * sig[0] + om[1] * sig[1]) + om[2] * sig[2]) + om[3] * sig[3];
+#pragma unroll
+            for (int j = 0; j < FIELD_MAXB; ++j) {
+                if (j < K) {
+                    if (a.weight_block) a.weight_block[idx * K + j] = om[j];
+                    if (a.sigma_block) a.sigma_block[idx * K + j] = sig[j];
+                }
+            }
+        }
+    }
+}
+
+static int scene_field_fill(SceneFieldBlock& b, const dreg_field_block& h)
+{
+    if (!h.center) return DREG_EINVAL;
+    for (int k = 0; k < 3; ++k) b.center[k] = h.center[k];
+    b.has_pose = h.pose != nullptr;
+    for (int k = 0; k < 9; ++k) b.R[k] = h.pose ? h.pose[k] : 0.f;
+    for (int k = 0; k < 3; ++k) b.t[k] = h.pose ? h.pose[9 + k] : 0.f;
+    // no ray is marched: no colour net, no scene interval (pair_field_fill's call)
+    return march_fill_block(b, h.binary, h.rx, h.ry, h.rz, nullptr, h.table, h.w1, h.w2, false, nullptr, nullptr, nullptr, h.offset, h.size, h.res, h.scale,
+                            h.hashed, h.roi_aabb, h.roi_aabb, h.model_aabb, 0.f, 0.f, 1.f, 0.f, false);
+}
+
+extern "C" {
+
+// The scene density of n_blocks blocks (HOST array `blocks`) at n points or at the nodes of a lattice; see include/dreg_nerf.h.
+int dreg_scene_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz, int n_blocks,
+                       const dreg_field_block* blocks, float power, float* sigma, float* weight_block, float* sigma_block, void* stream)
+{
+    if (n_blocks < 1 || n_blocks > FIELD_MAXB || !blocks) return DREG_EINVAL;
+    const bool lattice = origin != nullptr || spacing != nullptr;
+    if (n < 0 || !(power > 0.f) || !(power <= 3.0e38f)) return DREG_EINVAL;
+    if (lattice) {
+        if (x || !origin || !spacing) return DREG_EINVAL;
+        if (nx < 2 || ny < 2 || nz < 2 || nx > 1024 || ny > 1024 || nz > 1024 || (long)nx * ny * nz > (1l << 28)) return DREG_EINVAL;
+    } else if (n == 0) return DREG_OK;
+    if ((!lattice && !x) || !sigma) return DREG_EINVAL;
+    SceneFieldArgs a;
+    __builtin_memset(&a, 0, sizeof(a));
+    for (int b = 0; b < n_blocks; ++b)
+        if (scene_field_fill(a.b[b], blocks[b]) != DREG_OK) return DREG_EINVAL;
+    a.K = n_blocks;
+    for (int k = 0; k < 3; ++k) { a.origin[k] = lattice ? origin[k] : 0.f; a.spacing[k] = lattice ? spacing[k] : 0.f; }
+    a.half_power = 0.5f * power;
+    a.x = x;
+    a.nx = lattice ? nx : 0; a.ny = lattice ? ny : 1;
+    a.chunks_per_row = lattice ? (nx + 63) / 64 : 1;
+    a.n = lattice ? (long)nx * ny * nz : n;
+    a.chunks = lattice ? (long)a.chunks_per_row * ny * nz : (n + 63) / 64;
+    a.sigma = sigma; a.weight_block = weight_block; a.sigma_block = sigma_block;
+    const long waves = a.chunks < SCENE_FIELD_WAVES ? a.chunks : SCENE_FIELD_WAVES;
+    hipLaunchKernelGGL(scene_density_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+
+}  // extern "C"

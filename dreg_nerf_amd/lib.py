@@ -279,6 +279,8 @@ SIGNATURES = {
     "dreg_mc_emit": (I, [P, I, I, I, F, P, P, P, Z, P, P, I, I, P]),
     # pair_field.hip: x, n, origin, spacing, nx, ny, nz, the source block's arguments, the target block's, then pose, power, the five outputs, stream
     "dreg_pair_density": (I, [P, ctypes.c_long, P, P, I, I, I] + ([P, I, I, I] + [P] * 3 + [P] * 5 + [P] * 3) * 2 + [P, F] + [P] * 5 + [P]),
+    # scene_field.hip: x, n, origin, spacing, nx, ny, nz, n_blocks, blocks (HOST array of FieldBlock), power, sigma, weight_block, sigma_block, stream
+    "dreg_scene_density": (I, [P, ctypes.c_long, P, P, I, I, I, I, P, F, P, P, P, P]),
 }
 
 
@@ -339,6 +341,12 @@ class SceneBlock(ctypes.Structure):
     _fields_ = ([("origins", P), ("viewdirs", P), ("binary", P), ("rx", c_int), ("ry", c_int), ("rz", c_int), ("coarse_bits", P)] +
                 [(n, P) for n in ("table", "w1", "w2", "cw1", "cw2", "cw3", "offset", "size", "res", "scale", "hashed", "roi_aabb", "scene_aabb", "model_aabb")] +
                 [(n, c_float) for n in ("near_plane", "far_plane", "render_step_size", "alpha_thre")] + [("center", P)])
+
+
+class FieldBlock(ctypes.Structure):
+    """dreg_field_block of include/dreg_nerf.h (one block's arguments of dreg_scene_density)."""
+    _fields_ = ([("binary", P), ("rx", c_int), ("ry", c_int), ("rz", c_int)] +
+                [(n, P) for n in ("table", "w1", "w2", "offset", "size", "res", "scale", "hashed", "roi_aabb", "model_aabb", "center", "pose")])
 
 
 def load_probe():

@@ -6,7 +6,8 @@ both blocks rendered as one scene under the ground-truth and the predicted pose 
 blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / merged_mesh_gt.ply; with --merged_mesh_field the pair meshed as ONE density field, one closed surface per pose,
 merged_field_mesh_pred.ply / merged_field_mesh_gt.ply / merged_field_mesh.json; with --register_scene every scene registered as a
 whole — all ordered pairs of its blocks, pose synchronisation, scene_metrics_<split>.json — and with --render_scene all its blocks rendered as one
-scene under the ground-truth and the synchronised poses): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+scene under the ground-truth and the synchronised poses; with --scene_mesh_field all its blocks meshed as ONE density field under both
+pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_mesh.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -91,7 +92,7 @@ def write_ransac(d, split, rows, ransac_rows, ransac_refined_rows=None, log=prin
 
 
 def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer=None, metrics=None, log=print):
-    """--register_scene [--scene_robust] [--render_scene]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
+    """--register_scene [--scene_robust] [--render_scene] [--scene_mesh_field]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
     {scene: row of scene_metrics_{split}.json}.  Runs after the normal pass; get_scene, the forward calls and the synchronisation draw from no
     random stream.  pair_fn / renderer / metrics are scene_reg's injection points (tests)."""
     from dreg_nerf_amd import scene_reg
@@ -109,6 +110,17 @@ def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer
                 log(f"{name}: scene render of {len(scene)} blocks, aligned vs gt PSNR {mm['psnr_mean']:.2f} dB, SSIM {mm['ssim_mean']:.4f}", flush=True)
             else:
                 log(f"{name}: no NeRF blocks on disk, scene not rendered", flush=True)
+        if cfg.scene_mesh_field:   # all blocks as ONE density field (the scene --render_scene renders), one closed surface per pose set
+            paths = [b.get("nerf_path", "") for b in scene]
+            if all(p and os.path.exists(p) for p in paths):
+                from dreg_nerf_amd.scene_field import registered_scene_mesh
+                scene_dir = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", name)
+                st = registered_scene_mesh(scene_dir, scene, scene_reg.ground_truth(scene), res["G"], cfg.dataset, dev, cfg.mesh_resolution, cfg.mesh_level)["stats"]
+                log(f"{name}: scene field mesh of {st['K']} blocks, aligned V {st['aligned']['V']} F {st['aligned']['F']} area {st['aligned']['area']:.4f} volume "
+                    f"{st['aligned']['volume']:.4f}, gt V {st['gt']['V']} F {st['gt']['F']} area {st['gt']['area']:.4f} volume {st['gt']['volume']:.4f} -> "
+                    f"{scene_dir}/scene_field_mesh_{{aligned,gt}}.ply", flush=True)
+            else:
+                log(f"{name}: no NeRF blocks on disk, scene field mesh not written", flush=True)
     return rows
 
 
@@ -135,10 +147,16 @@ def init_distributed(local_rank: int):
     return local_rank
 
 
+def implied_flags(cfg):
+    """The flags other flags imply: the scene render and the scene mesh need the synchronised poses, so --render_scene and --scene_mesh_field each
+    imply --register_scene (and its scene_metrics file)."""
+    if cfg.render_scene or cfg.scene_mesh_field:
+        cfg.register_scene = True
+    return cfg
+
+
 def main():
-    cfg = config_parser()
-    if cfg.render_scene:
-        cfg.register_scene = True    # the scene render needs the synchronised poses: --render_scene implies --register_scene (and its scene_metrics file)
+    cfg = implied_flags(config_parser())
     if cfg.register_scene and cfg.synthetic > 0 and not 2 <= cfg.synthetic_blocks <= 4:
         raise SystemExit(f"--synthetic_blocks {cfg.synthetic_blocks}: a synthetic scene has 2 to 4 blocks")      # before the normal pass, not after it
     import random

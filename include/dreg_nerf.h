@@ -949,6 +949,33 @@ int dreg_pair_density(const float* x, long n, const float* origin, const float* 
                       const float* tgt_roi_aabb, const float* tgt_model_aabb, const float* tgt_center,
                       const float* pose, float power, float* sigma, float* w_src, float* w_tgt, float* sigma_src, float* sigma_tgt, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- a registered scene of K blocks as one density field
+ * (csrc/scene_field.hip; rule: DESIGN.md §3k) dreg_pair_density generalised to 1 <= n_blocks <= DREG_SCENE_MAX_BLOCKS blocks: the density of the
+ * scene dreg_ngp_render_scene renders, at points of the SCENE frame.  Block b contributes where its OWN occupancy cell is set; where several do
+ * they share the point by §3j's overlap weight (inverse distance to the blocks' camera centroids, the weights of the covering blocks summing to
+ * 1).  dreg_field_block holds ONE block's arguments of dreg_pair_density and its pose: 12 fp32 in HOST memory, R row-major then t, block -> scene
+ * (the caller's fp64 pose rounded once), or NULL: the block's frame is the scene's and the point is passed to it untouched.  `blocks` is a HOST
+ * array of n_blocks of them, read before the call returns.  Points form and lattice form, their limits and n == 0 as dreg_pair_density.
+ * Outputs on the device: sigma fp32 [n] = ((p_0 + p_1) + p_2) + p_3 with p_b = fl(omega_b sigma_b); optional (null = not written) weight_block
+ * fp32 [n, n_blocks] = omega_b (0 where block b does not cover the point, 1 where it alone does) and sigma_block fp32 [n, n_blocks] =
+ * m_b ? sigma_b : 0 (the block's dense-query density bit for bit).  One launch on `stream`, no atomics, never allocates: identical bytes between
+ * runs, point orders and the two forms.  DREG_EINVAL before any launch: n_blocks out of range, blocks null, a null in a block other than pose,
+ * and every condition dreg_pair_density rejects.  With n_blocks = 2 and blocks {(src, P), (tgt, NULL)} the outputs equal dreg_pair_density's bit
+ * for bit (weight_block = {w_src, w_tgt}, sigma_block = {sigma_src, sigma_tgt}). */
+typedef struct dreg_field_block {
+    const uint8_t* binary;
+    int rx, ry, rz;
+    const void *table, *w1, *w2;
+    const uint32_t *offset, *size, *res;
+    const float* scale;
+    const uint32_t* hashed;
+    const float *roi_aabb, *model_aabb, *center;
+    const float* pose;
+} dreg_field_block;
+int dreg_scene_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz,
+                       int n_blocks, const dreg_field_block* blocks, float power,
+                       float* sigma, float* weight_block, float* sigma_block, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
