@@ -1,6 +1,7 @@
 // What the ray marchers over a NeRF block's occupancy grid share (gfx950, wave64): the surface-visibility labels (visibility.hip), the volume
-// renderer (render.hip), its training backward (render_train.hip) and the two-block renderer (render_pair.hip).  All march one ray per lane,
-// 64 rays per wave.  Stated here once:
+// renderer (render.hip), its training backward (render_train.hip), the two-block and K-block renderers (render_pair.hip, render_scene.hip) and,
+// for the block rules, the density field of registered blocks (scene_field.hip).  The marchers run one ray per lane, 64 rays per wave.  Stated
+// here once:
 //   * MarchBlock, march_fill_block, march_pass_bound — one block as a marcher reads it, and the ONE host function that validates and fills it
 //                       from an entry point's arguments (nulls, grid dimensions, step, the 32,768-bit coarse rule, the scene diagonal and n_max);
 //   * march_load_coarse, march_grid — the device set-up: coarse bits into LDS, the MarchGrid of a block;
@@ -10,15 +11,25 @@
 //   * march_density   — the density of the wave's 64 samples: hash-grid gather per lane, then the 32 -> 64 -> 16 MLP on fp16 MFMA
 //                       through LDS (both stated in csrc/ngp_field.h, which the dense query of ngp.hip calls as well);
 //   * march_sigma, march_composite, march_color_row — a renderer's sample step: sigma -> alpha -> survival -> T_all -> w, T_s with
-//                       sigma_eff = omega sigma (omega = 1 outside render_pair.hip), then the colour net's input row of a survivor;
-//   * march_load_color_w, march_color, march_sigmoid_f16, render_ray_interval, render_sh4_f16 — the colour net and a renderer's ray set-up.
-// The bit-for-bit contracts between the kernels (pair == render, train(jitter 0) == render, persistent == lock-step labels) rest on these being
-// the same code.  Deliberately left apart:
+//                       sigma_eff = omega sigma (omega = 1 in the one-block renderers), then the colour net's input row of a survivor;
+//   * march_load_color_w, march_color, march_sigmoid_f16, render_ray_interval, render_sh4_f16 — the colour net and a renderer's ray set-up;
+//   * the rules of REGISTERED blocks (render_pair.hip, render_scene.hip, scene_field.hip):
+//     march_covered     — a block's own coverage of a point of its frame: inside the roi, the cell clamp(floor(u res), 0, res - 1) set;
+//     march_cursor_ray  — a ray's cursor of one block: its interval, act, n_lim, the empty interval [1, 0) on a miss;
+//     MarchAccum, march_accum_reset, march_sample_phase, march_write_ray, march_count_samples, march_report_overrun — the merged stream's
+//                       accumulator, the sample phase of one block (density, march_composite, colour row, colour net, accumulation; the per-block
+//                       share is the caller's), the common outputs of a ray and the kernel's tail (sample count, overrun report).
+// The bit-for-bit contracts between the kernels (pair == render, scene(K = 2) == pair, train(jitter 0) == render, persistent == lock-step labels)
+// rest on these being the same code.  Deliberately left apart:
 //   * surface_visibility_kernel keeps its own advance loop: it is the reference the persistent form is tested against;
 //   * vis_ray_setup keeps its own slab test: it has no parallel-axis case and no near / far, so its result on d[k] == 0 differs from
 //     render_ray_interval's;
 //   * visibility's sample update (best, stop_T) is another rule than march_composite and stays in visibility.hip;
-//   * render_pair.hip's block loop stays one non-unrolled body that reads the block from the kernel-argument segment (its header says why);
+//   * march_advance keeps its own copy of march_covered's lookup: there it is interleaved with the coarse-cell logic in the hot loop of four kernels;
+//   * the two renderers of registered blocks stay two kernels (K = 2 through the LDS cursors of render_scene.hip measured 1.39 x the register
+//     cursors of render_pair.hip); their block loops stay one non-unrolled body each that reads the block from the kernel-argument segment
+//     (render_pair.hip's header says why), and where a cursor lives and how the next sample is picked is each kernel's own;
+//   * the density phase of scene_field.hip is not march_density: it has no samples to refill and runs the gather not unrolled, at four waves;
 //   * two kernels at the edge of their budgets keep one helper's body written out, and say so where they do: ngp_render_bwd_kernel fills its
 //     MarchGrid itself (through march_grid it reserved more scratch), ngp_render_kernel its sample step (through march_composite / march_color_row
 //     its training forward measured slower).  The arithmetic is the helpers'; the bit-for-bit tests between the kernels hold it there.
@@ -378,3 +389,109 @@ __device__ __forceinline__ float march_sigmoid_f16(float pre)
     const float hv = (float)(_Float16)pre;
     return (float)(_Float16)__builtin_amdgcn_rcpf(1.f + __expf(-hv));
 }
+
+// ---- the rules of registered blocks, shared by the two-block and the K-block renderer and by the density field of registered blocks
+
+// Whether a block's own occupancy grid (binary uint8 [rdim], over the roi with low corner roi_lo and extents ext) covers the point x of the
+// block's frame: inside the roi on all axes (u = (x - lo) / ext, 0 <= u <= 1) and the cell clamp(floor(u res), 0, res - 1) set.
+__device__ __forceinline__ bool march_covered(const float* roi_lo, const float (&ext)[3], const int (&rdim)[3], const uint8_t* binary, const float (&x)[3])
+{
+    float u[3];
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { u[k] = (x[k] - roi_lo[k]) / ext[k]; inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
+    if (!inside) return false;
+    int ci[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)rdim[k]), 0), rdim[k] - 1);
+    return binary[((long)ci[0] * rdim[1] + ci[1]) * rdim[2] + ci[2]] != 0;
+}
+
+// A ray's cursor of block b, the ray given in the block's frame: act = the block is marched at all (the ray meets its scene aabb in a non-empty
+// interval), n_lim = the lattice samples of the interval at most; a ray that misses keeps the empty interval [1, 0): nothing is marched and
+// nothing is covered.  Each kernel stores the values where its cursor lives.
+__device__ __forceinline__ bool march_cursor_ray(const MarchBlock& b, const float* origins, const float* dirs, long ray, float (&o)[3], float (&d)[3], float& tmin,
+                                                 float& tmax, int& n_lim)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[k] = origins[ray * 3 + k]; d[k] = dirs[ray * 3 + k]; }
+    const bool hit = render_ray_interval(o, d, b.scene, b.near, b.far, tmin, tmax);
+    const bool act = hit && tmin < tmax;
+    n_lim = 0;
+    if (act) n_lim = (int)fminf(ceilf((tmax - tmin) / b.dt) + 1.f, (float)b.n_max);      // (n_max <= 1e8 + 2: the conversion cannot overflow)
+    else { tmin = 1.f; tmax = 0.f; }
+    return act;
+}
+
+// What a ray accumulates over the merged sample stream of its blocks; samples counts the lane's survivors over all its rays.
+struct MarchAccum {
+    float T_all, T_s, acc[3], opac, dep;
+    unsigned long long samples;
+};
+__device__ __forceinline__ void march_accum_reset(MarchAccum& r)      // a new ray (samples runs on)
+{
+    r.T_all = 1.f; r.T_s = 1.f; r.acc[0] = r.acc[1] = r.acc[2] = 0.f; r.opac = 0.f; r.dep = 0.f;
+}
+
+// Density, compositing and colour of the lanes whose sample is of block b (have), at position x of that block's frame with direction dir, ray
+// parameter tm and overlap weight omega: the per-sample arithmetic of ngp_render_kernel with sigma_eff = omega * sigma.  share(w) adds a
+// survivor's weight to the block's own share of the ray, which is the caller's.  Skipped wave-uniformly when no lane has a sample of b.
+template <class Share>
+__device__ __forceinline__ void march_sample_phase(const MarchBlock& b, float eps, bool have, const float (&x)[3], const float (&dir)[3], float tm, float omega,
+                                                   char* sX, char* sH, float* sOut, float* sO, MarchAccum& r, int lane, Share&& share)
+{
+    if (!__any(have)) return;
+    bool surv = false;
+    float w = 0.f;
+    {
+        NgpDensityW dw;
+        ngp_load_density_w(dw, b.w1, b.w2, lane);
+        const bool inside_m = march_density<true>(have, x, b.model, b.lv, b.table, dw, sX, sH, sOut, lane);
+        if (have) {
+            surv = march_composite(march_sigma(inside_m, sOut[lane]), omega, b.dt, eps, b.alpha_thre, r.T_all, r.T_s, w);
+            if (surv) {
+                uint32_t sh2[8];
+                render_sh4_f16(dir, sh2);
+                march_color_row(sX, lane, sh2);
+            }
+        }
+    }
+    if (__any(surv)) {
+        f16x8_t cw1f[4], cw3f[2];
+        march_load_color_w(cw1f, cw3f, b.cw1, b.cw3, lane);
+        march_color(sX, sH, sH, sO, cw1f, b.cw2, cw3f, lane);
+        if (surv) {
+            const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
+            const float pv[3] = {pre.x, pre.y, pre.z};
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) r.acc[ch] += w * march_sigmoid_f16(pv[ch]);
+            r.opac += w;
+            r.dep += w * tm;
+            share(w);
+            ++r.samples;
+        }
+    }
+    wave_sync();
+}
+
+// The outputs every renderer of registered blocks writes for a finished ray: rgb over the background, opacity, depth.
+__device__ __forceinline__ void march_write_ray(float* rgb, float* opacity, float* depth, const float (&bkgd)[3], long ray, const MarchAccum& r)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rgb[ray * 3 + k] = r.acc[k] + bkgd[k] * (1.f - r.opac);
+    opacity[ray] = r.opac;
+    depth[ray] = r.dep;
+}
+
+// The tail of a persistent renderer.  march_count_samples: the survivors this wave composited, one atomic per wave.  march_report_overrun, called
+// by lane 0 when the pass bound was reached with rays still queued or in flight: bit 63 of the ray counter (dreg_nerf_amd/render.py raises).
+// (Two functions, the second under the caller's condition: as one function's argument the queue pointer was read unconditionally and held in
+// SGPRs through the whole march.)
+__device__ __forceinline__ void march_count_samples(unsigned long long samples, unsigned long long* n_samples, int lane)
+{
+    unsigned long long tot = samples;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+    if (lane == 0 && tot) atomicAdd(n_samples, tot);
+}
+__device__ __forceinline__ void march_report_overrun(unsigned long long* queue) { atomicOr(queue, 1ull << 63); }

@@ -66,13 +66,8 @@ struct PairCursor {
 
 __device__ __forceinline__ void pair_take_ray(const PairBlock& b, PairCursor& c, long ray)
 {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { c.o[k] = b.origins[ray * 3 + k]; c.d[k] = b.dirs[ray * 3 + k]; }
-    const bool hit = render_ray_interval(c.o, c.d, b.scene, b.near, b.far, c.tmin, c.tmax);
-    c.act = hit && c.tmin < c.tmax;
-    c.pend = false; c.n = 0; c.n_lim = 0; c.tp = 0.f;
-    if (c.act) c.n_lim = (int)fminf(ceilf((c.tmax - c.tmin) / b.dt) + 1.f, (float)b.n_max);      // (n_max <= 1e8 + 2: the conversion cannot overflow)
-    else { c.tmin = 1.f; c.tmax = 0.f; }
+    c.act = march_cursor_ray(b, b.origins, b.dirs, ray, c.o, c.d, c.tmin, c.tmax, c.n_lim);
+    c.pend = false; c.n = 0; c.tp = 0.f;
 }
 
 // the cursor's next occupied lattice sample, if it has none pending (ngp_render_kernel's advance step)
@@ -90,69 +85,17 @@ __device__ __forceinline__ void pair_advance(const MarchGrid& g, const PairBlock
 // whether the block of cursor c covers the parameter t of its ray, x = o + t d: inside its interval, inside its roi, in an occupied fine cell
 __device__ __forceinline__ bool pair_covered(const MarchGrid& g, const PairCursor& c, float t, const float (&x)[3])
 {
-    if (!(t >= c.tmin && t < c.tmax)) return false;
-    float u[3];
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { u[k] = (x[k] - g.roi[k]) / g.roi_ext[k]; inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
-    if (!inside) return false;
-    int ci[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)g.rdim[k]), 0), g.rdim[k] - 1);
-    return g.binary[((long)ci[0] * g.ry + ci[1]) * g.rz + ci[2]] != 0;
+    return t >= c.tmin && t < c.tmax && march_covered(g.roi, g.roi_ext, g.rdim, g.binary, x);
 }
 
-struct PairAccum {
-    float T_all, T_s, acc[3], opac, dep, wsrc;
-    unsigned long long samples;
+struct PairAccum : MarchAccum {
+    float wsrc;                 // the source block's share: sum w over its samples
 };
 
 __device__ __forceinline__ void pair_write(const PairArgs& a, long ray, const PairAccum& r)
 {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.rgb[ray * 3 + k] = r.acc[k] + a.bkgd[k] * (1.f - r.opac);
-    a.opacity[ray] = r.opac;
-    a.depth[ray] = r.dep;
+    march_write_ray(a.rgb, a.opacity, a.depth, a.bkgd, ray, r);
     a.weight_src[ray] = r.wsrc;
-}
-
-// Density, compositing and colour of the lanes whose sample is of block b (have), at position x of that block's frame with direction dir,
-// ray parameter tm and overlap weight omega: the per-sample arithmetic of ngp_render_kernel with sigma_eff = omega * sigma.
-__device__ __forceinline__ void pair_phase(const PairArgs& a, const PairBlock& b, bool is_src, bool have, const float (&x)[3], const float (&dir)[3],
-                                           float tm, float omega, char* sX, char* sH, float* sOut, float* sO, PairAccum& r, int lane)
-{
-    if (!__any(have)) return;
-    bool surv = false;
-    float w = 0.f;
-    {
-        NgpDensityW dw;
-        ngp_load_density_w(dw, b.w1, b.w2, lane);
-        const bool inside_m = march_density<true>(have, x, b.model, b.lv, b.table, dw, sX, sH, sOut, lane);
-        if (have) {
-            surv = march_composite(march_sigma(inside_m, sOut[lane]), omega, b.dt, a.eps, b.alpha_thre, r.T_all, r.T_s, w);
-            if (surv) {
-                uint32_t sh2[8];
-                render_sh4_f16(dir, sh2);
-                march_color_row(sX, lane, sh2);
-            }
-        }
-    }
-    if (__any(surv)) {
-        f16x8_t cw1f[4], cw3f[2];
-        march_load_color_w(cw1f, cw3f, b.cw1, b.cw3, lane);
-        march_color(sX, sH, sH, sO, cw1f, b.cw2, cw3f, lane);
-        if (surv) {
-            const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
-            const float pv[3] = {pre.x, pre.y, pre.z};
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) r.acc[ch] += w * march_sigmoid_f16(pv[ch]);
-            r.opac += w;
-            r.dep += w * tm;
-            if (is_src) r.wsrc += w;
-            ++r.samples;
-        }
-    }
-    wave_sync();
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ngp_render_pair_kernel(PairArgs a)
@@ -180,7 +123,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     c0.tmin = c1.tmin = 1.f; c0.tmax = c1.tmax = 0.f; c0.tp = c1.tp = 0.f;
     c0.n = c1.n = 0; c0.n_lim = c1.n_lim = 0; c0.act = c1.act = false; c0.pend = c1.pend = false;
     PairAccum r;
-    r.T_all = 1.f; r.T_s = 1.f; r.acc[0] = r.acc[1] = r.acc[2] = 0.f; r.opac = 0.f; r.dep = 0.f; r.wsrc = 0.f; r.samples = 0;
+    march_accum_reset(r);
+    r.wsrc = 0.f; r.samples = 0;
 
     bool finished = false;
     for (long it = 0; it < a.pass_bound; ++it) {
@@ -195,8 +139,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                     ray = (long)q;
                     pair_take_ray(a.b[0], c0, ray);
                     pair_take_ray(a.b[1], c1, ray);
-                    r.T_all = 1.f; r.T_s = 1.f; r.opac = 0.f; r.dep = 0.f; r.wsrc = 0.f;
-                    r.acc[0] = r.acc[1] = r.acc[2] = 0.f;
+                    march_accum_reset(r);
+                    r.wsrc = 0.f;
                     if (c0.act || c1.act) live = true;
                     else pair_write(a, ray, r);
                 }
@@ -241,16 +185,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
         for (int k = 0; k < 3; ++k) { xp[k] = pick_s ? xs[k] : xt[k]; dp[k] = pick_s ? c0.d[k] : c1.d[k]; }
 #pragma unroll 1
-        for (int q = 0; q < 2; ++q) pair_phase(a, a.b[q], q == 0, q == 0 ? have_s : have_t, xp, dp, tm, omega, sX, sH, sOut, sO, r, lane);
+        for (int q = 0; q < 2; ++q)
+            march_sample_phase(a.b[q], a.eps, q == 0 ? have_s : have_t, xp, dp, tm, omega, sX, sH, sOut, sO, r, lane, [&](float w) { if (q == 0) r.wsrc += w; });
         if (ready && r.T_all < a.eps) { live = false; pair_write(a, ray, r); }           // transmittance below early_stop_eps: the ray ends
     }
-    // the survivors this wave composited: one atomic per wave
-    unsigned long long tot = r.samples;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
-    if (lane == 0 && tot) atomicAdd(a.n_samples, tot);
-    // the bound was reached with rays still queued or in flight: say so in bit 63 of the ray counter (dreg_nerf_amd/render.py raises)
-    if (!finished && lane == 0) atomicOr(a.queue, 1ull << 63);
+    march_count_samples(r.samples, a.n_samples, lane);
+    if (!finished && lane == 0) march_report_overrun(a.queue);
 }
 
 // One block's arguments as dreg_ngp_render takes them, plus the camera centroid.

@@ -59,17 +59,12 @@ enum { CUR_O = 0, CUR_D = 3, CUR_TMIN = 6, CUR_TMAX = 7, CUR_TP = 8, CUR_N = 9, 
 #define CURF(b, f) sCur[((b) * CUR_DW + (f)) * 64 + lane]
 #define CURI(b, f) reinterpret_cast<int*>(sCur)[((b) * CUR_DW + (f)) * 64 + lane]
 
-// the ray's cursor of block b (pair_take_ray of render_pair.hip); returns whether the block is marched at all
+// the ray's cursor of block b into its LDS column; returns whether the block is marched at all
 __device__ __forceinline__ bool scene_take_ray(const SceneBlock& b, float* sCur, int bi, long ray, int lane)
 {
     float o[3], d[3], tmin, tmax;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { o[k] = b.origins[ray * 3 + k]; d[k] = b.dirs[ray * 3 + k]; }
-    const bool hit = render_ray_interval(o, d, b.scene, b.near, b.far, tmin, tmax);
-    const bool act = hit && tmin < tmax;
-    int n_lim = 0;
-    if (act) n_lim = (int)fminf(ceilf((tmax - tmin) / b.dt) + 1.f, (float)b.n_max);      // (n_max <= 1e8 + 2: the conversion cannot overflow)
-    else { tmin = 1.f; tmax = 0.f; }
+    int n_lim;
+    const bool act = march_cursor_ray(b, b.origins, b.dirs, ray, o, d, tmin, tmax, n_lim);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { CURF(bi, CUR_O + k) = o[k]; CURF(bi, CUR_D + k) = d[k]; }
     CURF(bi, CUR_TMIN) = tmin; CURF(bi, CUR_TMAX) = tmax; CURF(bi, CUR_TP) = 0.f;
@@ -77,82 +72,23 @@ __device__ __forceinline__ bool scene_take_ray(const SceneBlock& b, float* sCur,
     return act;
 }
 
-// whether the block of grid g covers the point x of its ray (the parameter is already known to lie inside the block's interval): inside its roi,
-// in an occupied fine cell (pair_covered of render_pair.hip)
-__device__ __forceinline__ bool scene_covered(const MarchGrid& g, const float (&x)[3])
-{
-    float u[3];
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { u[k] = (x[k] - g.roi[k]) / g.roi_ext[k]; inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
-    if (!inside) return false;
-    int ci[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)g.rdim[k]), 0), g.rdim[k] - 1);
-    return g.binary[((long)ci[0] * g.ry + ci[1]) * g.rz + ci[2]] != 0;
-}
-
-struct SceneAccum {
-    float T_all, T_s, acc[3], opac, dep, wb[SCENE_MAXB];
-    unsigned long long samples;
+struct SceneAccum : MarchAccum {
+    float wb[SCENE_MAXB];       // the blocks' shares: sum w over the samples of each
 };
 
 __device__ __forceinline__ void scene_reset(SceneAccum& r)
 {
-    r.T_all = 1.f; r.T_s = 1.f; r.acc[0] = r.acc[1] = r.acc[2] = 0.f; r.opac = 0.f; r.dep = 0.f;
+    march_accum_reset(r);
 #pragma unroll
     for (int j = 0; j < SCENE_MAXB; ++j) r.wb[j] = 0.f;
 }
 
 __device__ __forceinline__ void scene_write(const SceneArgs& a, long ray, const SceneAccum& r)
 {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.rgb[ray * 3 + k] = r.acc[k] + a.bkgd[k] * (1.f - r.opac);
-    a.opacity[ray] = r.opac;
-    a.depth[ray] = r.dep;
+    march_write_ray(a.rgb, a.opacity, a.depth, a.bkgd, ray, r);
 #pragma unroll
     for (int j = 0; j < SCENE_MAXB; ++j)
         if (j < a.K) a.weight_block[ray * a.K + j] = r.wb[j];
-}
-
-// Density, compositing and colour of the lanes whose sample is of block q (have): pair_phase of render_pair.hip, with the weight of the sample
-// added to the block's own share (the other shares take + 0.f: the accumulators are not indexed at run time).
-__device__ __forceinline__ void scene_phase(const SceneArgs& a, const SceneBlock& b, int q, bool have, const float (&x)[3], const float (&dir)[3],
-                                            float tm, float omega, char* sX, char* sH, float* sOut, float* sO, SceneAccum& r, int lane)
-{
-    if (!__any(have)) return;
-    bool surv = false;
-    float w = 0.f;
-    {
-        NgpDensityW dw;
-        ngp_load_density_w(dw, b.w1, b.w2, lane);
-        const bool inside_m = march_density<true>(have, x, b.model, b.lv, b.table, dw, sX, sH, sOut, lane);
-        if (have) {
-            surv = march_composite(march_sigma(inside_m, sOut[lane]), omega, b.dt, a.eps, b.alpha_thre, r.T_all, r.T_s, w);
-            if (surv) {
-                uint32_t sh2[8];
-                render_sh4_f16(dir, sh2);
-                march_color_row(sX, lane, sh2);
-            }
-        }
-    }
-    if (__any(surv)) {
-        f16x8_t cw1f[4], cw3f[2];
-        march_load_color_w(cw1f, cw3f, b.cw1, b.cw3, lane);
-        march_color(sX, sH, sH, sO, cw1f, b.cw2, cw3f, lane);
-        if (surv) {
-            const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
-            const float pv[3] = {pre.x, pre.y, pre.z};
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) r.acc[ch] += w * march_sigmoid_f16(pv[ch]);
-            r.opac += w;
-            r.dep += w * tm;
-#pragma unroll
-            for (int j = 0; j < SCENE_MAXB; ++j) r.wb[j] += (j == q) ? w : 0.f;
-            ++r.samples;
-        }
-    }
-    wave_sync();
 }
 
 // (waves per SIMD 1..2: the registers are held to the pair kernel's budget of two waves, the 44.3 KB of LDS admit three workgroups per CU)
@@ -266,7 +202,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
                 for (int k = 0; k < 3; ++k) xo[k] = CURF(b, CUR_O + k) + tm * CURF(b, CUR_D + k);
                 MarchGrid g;
                 march_grid(g, a.b[b], sCoarse[b]);
-                if (!scene_covered(g, xo)) continue;
+                if (!march_covered(g.roi, g.roi_ext, g.rdim, g.binary, xo)) continue;
                 float d_oth = 0.f;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { const float e = xo[k] - a.b[b].center[k]; d_oth += e * e; }
@@ -282,16 +218,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
         }
         // ---- one body serves all blocks (the block's arguments are read per phase, not held)
 #pragma unroll 1
-        for (int q = 0; q < K; ++q) scene_phase(a, a.b[q], q, ready && pick == q, xp, dp, tm, omega, sX, sH, sOut, sO, r, lane);
+        for (int q = 0; q < K; ++q)
+            march_sample_phase(a.b[q], a.eps, ready && pick == q, xp, dp, tm, omega, sX, sH, sOut, sO, r, lane, [&](float w) {
+#pragma unroll
+                for (int j = 0; j < SCENE_MAXB; ++j) r.wb[j] += (j == q) ? w : 0.f;      // (the other shares take + 0.f: the accumulators are not indexed at run time)
+            });
         if (ready && r.T_all < a.eps) { live = false; scene_write(a, ray, r); }          // transmittance below early_stop_eps: the ray ends
     }
-    // the survivors this wave composited: one atomic per wave
-    unsigned long long tot = r.samples;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
-    if (lane == 0 && tot) atomicAdd(a.n_samples, tot);
-    // the bound was reached with rays still queued or in flight: say so in bit 63 of the ray counter (dreg_nerf_amd/render.py raises)
-    if (!finished && lane == 0) atomicOr(a.queue, 1ull << 63);
+    march_count_samples(r.samples, a.n_samples, lane);
+    if (!finished && lane == 0) march_report_overrun(a.queue);
 }
 
 static int scene_fill_block(SceneBlock& b, const dreg_scene_block& h)

@@ -1,14 +1,16 @@
 // The density of a REGISTERED SCENE of K NeRF blocks (1 <= K <= DREG_SCENE_MAX_BLOCKS = 4) as one scalar field, gfx950: the field the K-block
 // renderer (render_scene.hip) composites, evaluated at points or over a lattice in ONE kernel, so that the mesher
-// (marching_cubes.hip) extracts the surface of the whole registered scene (the K-block form of pair_field.hip; rule: DESIGN.md §3k, CPU
-// restatement: tests/scene_field_restatement.py).
+// (marching_cubes.hip) extracts the surface of the whole registered scene instead of K interleaved ones.  The ONE density-field kernel: the field
+// of a registered PAIR (dreg_pair_density; rule: DESIGN.md §3i, CPU restatement: tests/pair_field_restatement.py) is its K = 2 form, a second
+// entry point over the same launch (rule: DESIGN.md §3k, CPU restatement: tests/scene_field_restatement.py).
 //
-// Frames.  The field lives in the SCENE frame (the anchor's frame of pose_graph.synchronize).  Block b has a pose G_b = [R_b|t_b] mapping its frame
-// to the scene frame, rounded to fp32 once by the host (12 floats), or no pose.  For a point x (fp32):
-//   with a pose     d = x - t_b, x_b[k] = (R_b[0][k] d[0] + R_b[1][k] d[1]) + R_b[2][k] d[2]    (fp32, this order, no contraction: pair_field.hip's
-//                   expression, the same bits as torch fp32 elementwise ops)
+// Frames.  The field lives in the SCENE frame (the anchor's frame of pose_graph.synchronize; for a pair the TARGET frame).  Block b has a pose
+// G_b = [R_b|t_b] mapping its frame to the scene frame, rounded to fp32 once by the host (12 floats), or no pose.  For a point x (fp32):
+//   with a pose     d = x - t_b, x_b[k] = (R_b[0][k] d[0] + R_b[1][k] d[1]) + R_b[2][k] d[2]    (fp32, this order, no contraction: the same bits
+//                   as torch fp32 elementwise ops)
 //   without         x_b = x, the same bits
-// Own coverage     m_b(x_b): pair_field_covered's rule (inside the roi, the cell clamp(floor(u res), 0, res - 1) set)
+// Own coverage     m_b(x_b): march_covered (inside the roi, the cell clamp(floor(u res), 0, res - 1) set): a block contributes only where its OWN
+//                  occupancy cell is set (the renderer marches only occupied cells; floaters outside the grids are gone)
 // Densities        sigma_b = block b's density at x_b, the dense query's bit for bit (ngp_unit_cube, ngp_level_features, ngp_density_mlp,
 //                  __expf(h0 - 1) times the strictly-inside flag)
 // Weight           render_scene.hip's overlap weight, operation for operation: delta_b = |x_b - c_b|^2 + 1e-12f (the squares summed from 0.f in axis
@@ -17,15 +19,22 @@
 //                             omega_hi = 1 - omega_lo;
 //                  |C_b| >= 2: omega_b = 1 / (1 + sum over b' in C_b, ascending, of __expf(p/2 __logf(delta_b / delta_b')))
 // Scene density    sigma = ((p_0 + p_1) + p_2) + p_3 with p_b = fl(omega_b sigma_b); absent or uncovered blocks contribute + 0.f (every term is >= 0:
-//                  adding + 0.f changes no bit).  With K = 2 and blocks [(src, P), (tgt, none)] every output is dreg_pair_density's, bit for bit.
+//                  adding + 0.f changes no bit).  Where one block alone covers the point sigma is that block's sigma exactly.
+// The pair         K = 2, blocks [(src, P), (tgt, none)]: w_S = omega_0 = m_S ? (m_T ? w : 1) : 0 with w = 1 / (1 + __expf(p/2 __logf(delta_S /
+//                  delta_T))), w_T = omega_1 = m_T ? (m_S ? 1 - w : 1) : 0, sigma_P = fl(fl(w_S sigma_S) + fl(w_T sigma_T)).
 //
-// One lane = one point, 64 points per wave, one-wave workgroups that stride over the 64-point chunks; points form and lattice form as
-// pair_density_kernel.  Per chunk: the positions and all K coverages (a bit mask per lane) and distances, then the weights, then block b's
-// density phase (its MFMA operands, the 16-level gather, the MLP through the one 64 x 64 fp16 LDS tile) only when some lane has m_b set.  Every
-// loop over the block index that reads a block is ONE non-unrolled body that reads the block and its pose from the kernel-argument segment, for
-// the reason render_pair.hip's header gives.  Nothing per-lane is indexed by a run-time block index (that would go to scratch): delta_b, sigma_b
-// and omega_b sit in K named registers, written by select inside unrolled loops, and x_b is recomputed in the phase from the same operands (the
-// same bits).  No atomics, no process-global state; a point's result depends on nothing but the point.  As built: DESIGN.md §3k.
+// One lane = one point, 64 points per wave, one-wave workgroups that stride over the 64-point chunks (ngp_density_kernel's shape).  Points form:
+// chunk c holds points 64 c .. 64 c + 63 of x [N,3].  Lattice form: lanes run along x — a chunk is 64 x-contiguous nodes of one (y,z) row, the
+// lane forms its node's position origin_c + (float)i_c * spacing_c itself (the position dreg_mc_emit gives the node), output [nz,ny,nx]; no
+// position tensor exists.  Per chunk: the positions and all K coverages (a bit mask per lane) and distances, then the weights, then block b's
+// density phase (its MFMA operands, the 16-level gather, the MLP through the one 64 x 64 fp16 LDS tile) only when some lane has m_b set, so a
+// chunk outside every grid costs the K lookups and a store.  Every loop over the block index that reads a block is ONE non-unrolled body that
+// reads the block and its pose from the kernel-argument segment, for the reason render_pair.hip's header gives.  Nothing per-lane is indexed by
+// a run-time block index (that would go to scratch): delta_b, sigma_b and omega_b sit in K named registers, written by select inside unrolled
+// loops, and x_b is recomputed in the phase from the same operands (the same bits).  The per-block parts go out through one nullable pointer per
+// block and array and one stride: [n,K] rows for the scene entry, four separate [n] arrays for the pair entry.  No atomics, no process-global
+// state; a point's result depends on nothing but the point, so the output is bit-identical between runs, launch widths, orders and forms.  As
+// built: DESIGN.md §3k.
 #include "march.h"
 #include "../../include/dreg_nerf.h"   // dreg_field_block, DREG_SCENE_MAX_BLOCKS and the signature check of the entry point defined here
 
@@ -47,11 +56,13 @@ struct SceneFieldArgs {
     int chunks_per_row;         // lattice form: ceil(nx / 64)
     long n;                     // points, or nodes (nx ny nz)
     long chunks;                // 64-point chunks of the launch
-    float *sigma, *weight_block, *sigma_block;      // the last two may be null; [n,K]
+    float* sigma;               // [n]
+    float *weight_out[FIELD_MAXB], *sigma_out[FIELD_MAXB];     // block j's omega_j / sigma_j of point i at [i * part_stride]; each may be null
+    long part_stride;
 };
 static_assert(sizeof(SceneFieldArgs) <= 4096, "the blocks are read from the kernel-argument segment");
 
-static constexpr long SCENE_FIELD_WAVES = 16384;    // one-wave workgroups of the launch at most (pair_density_kernel's width)
+static constexpr long SCENE_FIELD_WAVES = 16384;    // one-wave workgroups of the launch at most (256 CUs x 16 resident x 4 rounds)
 
 // the scene-frame point x in block b's frame
 __device__ __forceinline__ void scene_field_to_block(const SceneFieldBlock& b, const float (&x)[3], float (&xb)[3])
@@ -66,25 +77,20 @@ __device__ __forceinline__ void scene_field_to_block(const SceneFieldBlock& b, c
     }
 }
 
-// whether block b's own occupancy grid covers the point x of its frame (pair_field_covered of pair_field.hip, restated: that file is not edited)
+// whether block b's own occupancy grid covers the point x of its frame (the extents as march_grid forms them: the same fp32 subtraction)
 __device__ __forceinline__ bool scene_field_covered(const MarchBlock& b, const float (&x)[3])
 {
     const int rdim[3] = {b.rx, b.ry, b.rz};
-    float u[3];
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { u[k] = (x[k] - b.roi[k]) / (b.roi[3 + k] - b.roi[k]); inside = inside && u[k] >= 0.f && u[k] <= 1.f; }
-    if (!inside) return false;
-    int ci[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ci[k] = min(max((int)floorf(u[k] * (float)rdim[k]), 0), rdim[k] - 1);
-    return b.binary[((long)ci[0] * b.ry + ci[1]) * b.rz + ci[2]] != 0;
+    const float ext[3] = {b.roi[3] - b.roi[0], b.roi[4] - b.roi[1], b.roi[5] - b.roi[2]};
+    return march_covered(b.roi, ext, rdim, b.binary, x);
 }
 
-// (the pair kernel's residency: four waves per SIMD, what the 9.25 KB of LDS per wave admit)
+// four waves per SIMD, the residency the 9.25 KB of LDS per wave admit (16 workgroups per CU): without the attribute the two-block form of this
+// kernel took 79 VGPRs + 64 AGPRs, three waves per SIMD; the gathers of a phase are latency, which occupancy hides
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void scene_density_kernel(SceneFieldArgs a)
 {
-    // ONE 64 x 64 fp16 tile per wave, the encoded input in its first rows until the first layer has read it (pair_density_kernel's layout)
+    // ONE 64 x 64 fp16 tile per wave, the encoded input in its first rows until the first layer has read it (ngp_density_kernel's layout:
+    // allowed by ngp_density_mlp, the epilogue below writes sOut only)
     __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];
     __shared__ float sOut[64];
     char* sX = sH;
@@ -189,11 +195,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         if (valid) {
             a.sigma[idx] = ((om[0] * sig[0] + om[1] * sig[1]) + om[2] * sig[2]) + om[3] * sig[3];
 #pragma unroll
-            for (int j = 0; j < FIELD_MAXB; ++j) {
-                if (j < K) {
-                    if (a.weight_block) a.weight_block[idx * K + j] = om[j];
-                    if (a.sigma_block) a.sigma_block[idx * K + j] = sig[j];
-                }
+            for (int j = 0; j < FIELD_MAXB; ++j) {           // (the pointers of blocks >= K are null)
+                if (a.weight_out[j]) a.weight_out[j][idx * a.part_stride] = om[j];
+                if (a.sigma_out[j]) a.sigma_out[j][idx * a.part_stride] = sig[j];
             }
         }
     }
@@ -206,18 +210,17 @@ static int scene_field_fill(SceneFieldBlock& b, const dreg_field_block& h)
     b.has_pose = h.pose != nullptr;
     for (int k = 0; k < 9; ++k) b.R[k] = h.pose ? h.pose[k] : 0.f;
     for (int k = 0; k < 3; ++k) b.t[k] = h.pose ? h.pose[9 + k] : 0.f;
-    // no ray is marched: no colour net, no scene interval (pair_field_fill's call)
+    // no ray is marched: no colour net, no scene interval (the roi stands in for the scene aabb, the step for a positive number)
     return march_fill_block(b, h.binary, h.rx, h.ry, h.rz, nullptr, h.table, h.w1, h.w2, false, nullptr, nullptr, nullptr, h.offset, h.size, h.res, h.scale,
                             h.hashed, h.roi_aabb, h.roi_aabb, h.model_aabb, 0.f, 0.f, 1.f, 0.f, false);
 }
 
-extern "C" {
-
-// The scene density of n_blocks blocks (HOST array `blocks`) at n points or at the nodes of a lattice; see include/dreg_nerf.h.
-int dreg_scene_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz, int n_blocks,
-                       const dreg_field_block* blocks, float power, float* sigma, float* weight_block, float* sigma_block, void* stream)
+// The ONE launch behind both entry points, and the one statement of the forms, the lattice limits, the chunk counts and the launch width.
+// weight_out / sigma_out: n_blocks pointers each (any may be null: not written), block j's value of point i at [i * part_stride].
+static int scene_density_launch(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz, int n_blocks,
+                                const dreg_field_block* blocks, float power, float* sigma, float* const* weight_out, float* const* sigma_out,
+                                long part_stride, void* stream)
 {
-    if (n_blocks < 1 || n_blocks > FIELD_MAXB || !blocks) return DREG_EINVAL;
     const bool lattice = origin != nullptr || spacing != nullptr;
     if (n < 0 || !(power > 0.f) || !(power <= 3.0e38f)) return DREG_EINVAL;
     if (lattice) {
@@ -237,11 +240,47 @@ int dreg_scene_density(const float* x, long n, const float* origin, const float*
     a.chunks_per_row = lattice ? (nx + 63) / 64 : 1;
     a.n = lattice ? (long)nx * ny * nz : n;
     a.chunks = lattice ? (long)a.chunks_per_row * ny * nz : (n + 63) / 64;
-    a.sigma = sigma; a.weight_block = weight_block; a.sigma_block = sigma_block;
+    a.sigma = sigma;
+    for (int b = 0; b < n_blocks; ++b) { a.weight_out[b] = weight_out[b]; a.sigma_out[b] = sigma_out[b]; }
+    a.part_stride = part_stride;
     const long waves = a.chunks < SCENE_FIELD_WAVES ? a.chunks : SCENE_FIELD_WAVES;
     hipLaunchKernelGGL(scene_density_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
     DREG_LAUNCH_CHECK();
     return DREG_OK;
+}
+
+extern "C" {
+
+// The scene density of n_blocks blocks (HOST array `blocks`) at n points or at the nodes of a lattice; see include/dreg_nerf.h.
+int dreg_scene_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz, int n_blocks,
+                       const dreg_field_block* blocks, float power, float* sigma, float* weight_block, float* sigma_block, void* stream)
+{
+    if (n_blocks < 1 || n_blocks > FIELD_MAXB || !blocks) return DREG_EINVAL;
+    float *w[FIELD_MAXB], *s[FIELD_MAXB];                    // [n,K] rows: block j's column
+    for (int j = 0; j < n_blocks; ++j) { w[j] = weight_block ? weight_block + j : nullptr; s[j] = sigma_block ? sigma_block + j : nullptr; }
+    return scene_density_launch(x, n, origin, spacing, nx, ny, nz, n_blocks, blocks, power, sigma, w, s, n_blocks, stream);
+}
+
+// The pair density: the K = 2 form, blocks {(src, pose), (tgt, none)}, the parts in four separate [n] arrays; see include/dreg_nerf.h.
+int dreg_pair_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz,
+                      const uint8_t* src_binary, int src_rx, int src_ry, int src_rz, const void* src_table, const void* src_w1, const void* src_w2,
+                      const uint32_t* src_offset, const uint32_t* src_size, const uint32_t* src_res, const float* src_scale, const uint32_t* src_hashed,
+                      const float* src_roi_aabb, const float* src_model_aabb, const float* src_center,
+                      const uint8_t* tgt_binary, int tgt_rx, int tgt_ry, int tgt_rz, const void* tgt_table, const void* tgt_w1, const void* tgt_w2,
+                      const uint32_t* tgt_offset, const uint32_t* tgt_size, const uint32_t* tgt_res, const float* tgt_scale, const uint32_t* tgt_hashed,
+                      const float* tgt_roi_aabb, const float* tgt_model_aabb, const float* tgt_center,
+                      const float* pose, float power, float* sigma, float* w_src, float* w_tgt, float* sigma_src, float* sigma_tgt, void* stream)
+{
+    // the source block must have a pose (the scene entry takes a block without one); points form with n == 0 stays DREG_OK before any null check
+    if (!pose && (origin || spacing || n != 0)) return DREG_EINVAL;
+    const dreg_field_block blocks[2] = {
+        {src_binary, src_rx, src_ry, src_rz, src_table, src_w1, src_w2, src_offset, src_size, src_res, src_scale, src_hashed, src_roi_aabb, src_model_aabb,
+         src_center, pose},
+        {tgt_binary, tgt_rx, tgt_ry, tgt_rz, tgt_table, tgt_w1, tgt_w2, tgt_offset, tgt_size, tgt_res, tgt_scale, tgt_hashed, tgt_roi_aabb, tgt_model_aabb,
+         tgt_center, nullptr}};
+    float* const w[2] = {w_src, w_tgt};
+    float* const s[2] = {sigma_src, sigma_tgt};
+    return scene_density_launch(x, n, origin, spacing, nx, ny, nz, 2, blocks, power, sigma, w, s, 1, stream);
 }
 
 }  // extern "C"

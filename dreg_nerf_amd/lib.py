@@ -277,7 +277,7 @@ SIGNATURES = {
     "dreg_mc_workspace_bytes": (Z, [I, I, I]),
     "dreg_mc_count": (I, [P, I, I, I, F, P, Z, P, P]),
     "dreg_mc_emit": (I, [P, I, I, I, F, P, P, P, Z, P, P, I, I, P]),
-    # pair_field.hip: x, n, origin, spacing, nx, ny, nz, the source block's arguments, the target block's, then pose, power, the five outputs, stream
+    # scene_field.hip, the K = 2 entry: x, n, origin, spacing, nx, ny, nz, the source block's arguments, the target block's, then pose, power, the five outputs, stream
     "dreg_pair_density": (I, [P, ctypes.c_long, P, P, I, I, I] + ([P, I, I, I] + [P] * 3 + [P] * 5 + [P] * 3) * 2 + [P, F] + [P] * 5 + [P]),
     # scene_field.hip: x, n, origin, spacing, nx, ny, nz, n_blocks, blocks (HOST array of FieldBlock), power, sigma, weight_block, sigma_block, stream
     "dreg_scene_density": (I, [P, ctypes.c_long, P, P, I, I, I, I, P, F, P, P, P, P]),

@@ -1,5 +1,5 @@
-"""A registered pair of NeRF blocks as ONE density field, and its surface mesh: the fused kernel of csrc/pair_field.hip under the marching-cubes
-kernels of csrc/marching_cubes.hip.  The field is the scene the two-block renderer composites (render.render_pair_image): a block
+"""A registered pair of NeRF blocks as ONE density field, and its surface mesh: the fused kernel of csrc/scene_field.hip in its K = 2 form
+(dreg_pair_density; the lattice, the blend and the torch helpers are scene_field.py's) under the marching-cubes kernels of csrc/marching_cubes.hip.  The field is the scene the two-block renderer composites (render.render_pair_image): a block
 contributes where its own occupancy cell is set, and where both do they share the point by the overlap weight.  Rule, kernel and measurements:
 DESIGN.md §3i; CPU restatement: tests/pair_field_restatement.py."""
 import math
@@ -10,83 +10,24 @@ import torch
 
 from . import lib as L
 from . import mesh as M
-
-MAX_DIM, MAX_NODES = 1024, 1 << 28      # dreg_pair_density's and dreg_mc_count's lattice limits
-
-
-def _pose34(pose) -> np.ndarray:
-    """A [3,4] or [4,4] pose as fp64 [3,4] on the host."""
-    P = (pose.detach().double().cpu().numpy() if torch.is_tensor(pose) else np.asarray(pose, dtype=np.float64)).reshape(-1, 4)
-    if P.shape[0] not in (3, 4):
-        raise ValueError(f"pose must be [3,4] or [4,4], got {tuple(P.shape)}")
-    return P[:3].copy()
-
-
-def _f32_up(v: float) -> float:
-    f = np.float32(v)
-    return float(f if float(f) >= v else np.nextafter(f, np.float32(np.inf)))
-
-
-def _f32_down(v: float) -> float:
-    f = np.float32(v)
-    return float(f if float(f) <= v else np.nextafter(f, np.float32(-np.inf)))
+from .scene_field import _lattice_dims, _pose34, blend_scene_attributes, grid_covered, points_to_frame, scene_lattice
 
 
 def pair_lattice(src_aabb, tgt_aabb, pose, resolution: int):
-    """(origin, spacing, (nx, ny, nz)) of the lattice a pair is meshed on, in the TARGET frame.  In fp64: the box of the target model aabb together
-    with the eight corners of the source model aabb moved by the pose; h = its longest extent / resolution (cubic cells); origin = lo - h and
-    n_k = ceil(ext_k / h) + 3 nodes (resolution + 3 on the longest axis), so the first and the last node of every axis lie at least h outside both
-    aabbs: the lattice's shell is exactly 0 and every level > 0 gives a closed mesh.  origin and spacing are fp32-exact Python floats; the
-    rounding is directed (h up, after one part in 2^20 is added to it; origin down from lo - h) so that it cannot eat the margin.  ValueError when
-    a dimension exceeds 1024 or the nodes exceed 2^28."""
-    if int(resolution) < 1:
-        raise ValueError(f"pair_lattice: resolution {resolution} must be >= 1")
-    resolution = int(resolution)
-    P = _pose34(pose)
-    s = np.asarray([float(v) for v in (src_aabb.tolist() if torch.is_tensor(src_aabb) else src_aabb)], dtype=np.float64)
-    t = np.asarray([float(v) for v in (tgt_aabb.tolist() if torch.is_tensor(tgt_aabb) else tgt_aabb)], dtype=np.float64)
-    corners = np.array([[s[3 * i], s[3 * j + 1], s[3 * k + 2]] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
-    moved = corners @ P[:, :3].T + P[:, 3]
-    lo = np.minimum(moved.min(axis=0), t[:3])
-    hi = np.maximum(moved.max(axis=0), t[3:])
-    ext = hi - lo
-    if not (np.isfinite(ext).all() and ext.max() > 0):
-        raise ValueError("pair_lattice: the aabbs span no volume")
-    h = float(ext.max()) / resolution
-    longest = int(np.argmax(ext))
-    dims = tuple(resolution + 3 if k == longest else int(math.ceil(ext[k] / h)) + 3 for k in range(3))
-    if max(dims) > MAX_DIM:
-        raise ValueError(f"pair_lattice: {dims[0]} x {dims[1]} x {dims[2]} nodes: a dimension exceeds {MAX_DIM}")
-    if dims[0] * dims[1] * dims[2] > MAX_NODES:
-        raise ValueError(f"pair_lattice: {dims[0]} x {dims[1]} x {dims[2]} nodes exceed 2^28")
-    h32 = _f32_up(h * (1.0 + 2.0 ** -20))
-    origin = [_f32_down(float(lo[k]) - h32) for k in range(3)]
-    return origin, [h32, h32, h32], dims
+    """(origin, spacing, (nx, ny, nz)) of the lattice a pair is meshed on, in the TARGET frame: scene_lattice over the target model aabb and the
+    source model aabb moved by the pose."""
+    return scene_lattice([src_aabb, tgt_aabb], [pose, None], resolution)
 
 
 def blend_vertex_attributes(w_src, w_tgt, sigma_src, sigma_tgt, R, grad_src, grad_tgt, color_src=None, color_tgt=None):
-    """Per-vertex attributes of a pair mesh from the two blocks' own, all [V] / [V,3] tensors of one dtype: with a_b = w_b sigma_b,
-    g = w_S R grad_S + w_T grad_T (grad_S in the source frame; the gradient of the overlap weight is ignored), normal = -g / |g| (zeros where g
-    vanishes or is not finite); colour = (a_S c_S + a_T c_T) / (a_S + a_T) (one block's own colour, bit for bit, where the other's a is 0) and
-    weight_src = a_S / (a_S + a_T), both zeros where the denominator is 0.  Returns (normals, colors or None, weight_src)."""
-    R = torch.as_tensor(R, dtype=grad_src.dtype, device=grad_src.device)
-    moved = torch.stack([R[k, 0] * grad_src[:, 0] + R[k, 1] * grad_src[:, 1] + R[k, 2] * grad_src[:, 2] for k in range(3)], dim=1)   # elementwise: no GEMM library in the path
-    g = w_src[:, None] * moved + w_tgt[:, None] * grad_tgt
-    norm = g.norm(dim=1, keepdim=True)
-    ok = (norm > 0) & torch.isfinite(norm)
-    normals = torch.where(ok, -g / torch.where(ok, norm, torch.ones_like(norm)), torch.zeros_like(g))
-    a_s, a_t = w_src * sigma_src, w_tgt * sigma_tgt
-    den = a_s + a_t
-    has = den > 0
-    safe = torch.where(has, den, torch.ones_like(den))
-    weight_src = torch.where(has, a_s / safe, torch.zeros_like(den))
-    colors = None
-    if color_src is not None and color_tgt is not None:
-        mix = (a_s[:, None] * color_src + a_t[:, None] * color_tgt) / safe[:, None]
-        # where one block alone carries the density the colour is that block's own, bit for bit ((a c) / a may differ from c by a rounding)
-        mix = torch.where((a_t == 0)[:, None], color_src, torch.where((a_s == 0)[:, None], color_tgt, mix))
-        colors = torch.where(has[:, None], mix, torch.zeros_like(color_src))
-    return normals, colors, weight_src
+    """Per-vertex attributes of a pair mesh from the two blocks' own, all [V] / [V,3] tensors of one dtype: blend_scene_attributes with K = 2 and
+    the source block's rotation R.  With a_b = w_b sigma_b, g = w_S R grad_S + w_T grad_T (grad_S in the source frame), normal = -g / |g|; colour
+    = (a_S c_S + a_T c_T) / (a_S + a_T) (one block's own colour, bit for bit, where the other's a is 0) and weight_src = a_S / (a_S + a_T), zeros
+    where a denominator is 0.  Returns (normals, colors or None, weight_src)."""
+    colors = None if color_src is None or color_tgt is None else [color_src, color_tgt]
+    normals, colors, share = blend_scene_attributes(torch.stack([w_src, w_tgt], dim=1), torch.stack([sigma_src, sigma_tgt], dim=1), [R, None],
+                                                    [grad_src, grad_tgt], colors)
+    return normals, colors, share[:, 0]
 
 
 class PairField:
@@ -150,30 +91,19 @@ class PairField:
     @torch.no_grad()
     def sample_lattice(self, origin, spacing, dims) -> torch.Tensor:
         """The pair density at the nodes origin + (float)i * spacing of an nx x ny x nz lattice: fp32 [nz,ny,nx].  No position tensor is formed."""
-        nx, ny, nz = (int(v) for v in dims)
-        if min(nx, ny, nz) < 2 or max(nx, ny, nz) > MAX_DIM or nx * ny * nz > MAX_NODES:
-            raise ValueError(f"sample_lattice: lattice {nx} x {ny} x {nz}: every dimension must be in [2, 1024] and the nodes at most 2^28")
+        nx, ny, nz = _lattice_dims(dims)
         return self._run(None, nx * ny * nz, origin, spacing, (nx, ny, nz), False)[0].view(nz, ny, nx)
 
     def lattice(self, resolution: int):
         return pair_lattice(self.src._aabb_host(), self.tgt._aabb_host(), self.pose, resolution)
 
     def covered(self, k: int, x: torch.Tensor) -> torch.Tensor:
-        """Own coverage m_b of block k (0 = source, 1 = target) at x [N,3] fp32 of THAT block's frame, in torch fp32 elementwise ops: inside the
-        occupancy roi (0 <= u <= 1 on all axes) and the cell clamp(floor(u res), 0, res - 1) set.  Not the hot path (tools, composition baseline)."""
-        roi, b8 = self._grids[k]
-        lo = x.new_tensor(roi[:3])
-        u = (x - lo) / (x.new_tensor(roi[3:]) - lo)
-        inside = ((u >= 0) & (u <= 1)).all(dim=1)
-        res = x.new_tensor([float(v) for v in b8.shape])
-        ci = torch.minimum(torch.floor(torch.where(inside[:, None], u, torch.zeros_like(u)) * res).clamp(min=0), res - 1).long()
-        return inside & (b8[ci[:, 0], ci[:, 1], ci[:, 2]] != 0)
+        """Own coverage m_b of block k (0 = source, 1 = target) at x [N,3] fp32 of THAT block's frame (scene_field.grid_covered)."""
+        return grid_covered(*self._grids[k], x)
 
     def points_to_source(self, x: torch.Tensor) -> torch.Tensor:
-        """x [N,3] fp32 of the target frame in the source frame, by the kernel's own expression in torch fp32 elementwise ops (the same bits)."""
-        Rf, tf = self.R, self.t
-        d = [x[:, k] - float(tf[k]) for k in range(3)]
-        return torch.stack([(float(Rf[0, k]) * d[0] + float(Rf[1, k]) * d[1]) + float(Rf[2, k]) * d[2] for k in range(3)], dim=1)
+        """x [N,3] fp32 of the target frame in the source frame (scene_field.points_to_frame: the kernel's bits)."""
+        return points_to_frame(self.R, self.t, x)
 
 
 @torch.no_grad()

@@ -1,7 +1,8 @@
 """A registered SCENE of K NeRF blocks (1 <= K <= 4) as ONE density field, and its surface mesh: the fused kernel of csrc/scene_field.hip under the
 marching-cubes kernels of csrc/marching_cubes.hip.  The field is the scene the K-block renderer composites (render.render_scene_image, DESIGN.md
-§3j): a block contributes where its own occupancy cell is set, and where several do they share the point by the overlap weight.  The K-block form
-of pair_field.py; rule, kernel and measurements: DESIGN.md §3k; CPU restatement: tests/scene_field_restatement.py."""
+§3j): a block contributes where its own occupancy cell is set, and where several do they share the point by the overlap weight.  The
+pair's field (pair_field.py) is the K = 2 form and takes its lattice, blend and helpers from here; rule, kernel and measurements: DESIGN.md §3k;
+CPU restatement: tests/scene_field_restatement.py."""
 import ctypes
 import math
 from typing import Optional
@@ -11,14 +12,62 @@ import torch
 
 from . import lib as L
 from . import mesh as M
-from .pair_field import MAX_DIM, MAX_NODES, _f32_down, _f32_up, _pose34
+
+MAX_DIM, MAX_NODES = 1024, 1 << 28      # the density entries' and dreg_mc_count's lattice limits
+
+
+def _pose34(pose) -> np.ndarray:
+    """A [3,4] or [4,4] pose as fp64 [3,4] on the host."""
+    P = (pose.detach().double().cpu().numpy() if torch.is_tensor(pose) else np.asarray(pose, dtype=np.float64)).reshape(-1, 4)
+    if P.shape[0] not in (3, 4):
+        raise ValueError(f"pose must be [3,4] or [4,4], got {tuple(P.shape)}")
+    return P[:3].copy()
+
+
+def _f32_up(v: float) -> float:
+    f = np.float32(v)
+    return float(f if float(f) >= v else np.nextafter(f, np.float32(np.inf)))
+
+
+def _f32_down(v: float) -> float:
+    f = np.float32(v)
+    return float(f if float(f) <= v else np.nextafter(f, np.float32(-np.inf)))
+
+
+def _lattice_dims(dims):
+    """(nx, ny, nz) as ints, refused as the density entries refuse them."""
+    nx, ny, nz = (int(v) for v in dims)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) > MAX_DIM or nx * ny * nz > MAX_NODES:
+        raise ValueError(f"sample_lattice: lattice {nx} x {ny} x {nz}: every dimension must be in [2, 1024] and the nodes at most 2^28")
+    return nx, ny, nz
+
+
+def grid_covered(roi, b8: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """Own coverage of a block with occupancy b8 (uint8 [rx,ry,rz]) over roi (6 host floats) at x [N,3] fp32 of THAT block's frame, in torch fp32
+    elementwise ops: inside the roi (0 <= u <= 1 on all axes) and the cell clamp(floor(u res), 0, res - 1) set.  Not the hot path (tools,
+    composition baseline)."""
+    lo = x.new_tensor(roi[:3])
+    u = (x - lo) / (x.new_tensor(roi[3:]) - lo)
+    inside = ((u >= 0) & (u <= 1)).all(dim=1)
+    res = x.new_tensor([float(v) for v in b8.shape])
+    ci = torch.minimum(torch.floor(torch.where(inside[:, None], u, torch.zeros_like(u)) * res).clamp(min=0), res - 1).long()
+    return inside & (b8[ci[:, 0], ci[:, 1], ci[:, 2]] != 0)
+
+
+def points_to_frame(Rf, tf, x: torch.Tensor) -> torch.Tensor:
+    """x [N,3] fp32 of the scene frame in the frame of a block with the fp32 pose [Rf|tf] (block -> scene), by the kernel's own expression in
+    torch fp32 elementwise ops (the same bits)."""
+    d = [x[:, k] - float(tf[k]) for k in range(3)]
+    return torch.stack([(float(Rf[0, k]) * d[0] + float(Rf[1, k]) * d[1]) + float(Rf[2, k]) * d[2] for k in range(3)], dim=1)
 
 
 def scene_lattice(aabbs, poses, resolution: int):
-    """(origin, spacing, (nx, ny, nz)) of the lattice a scene is meshed on, in the SCENE frame: pair_field.pair_lattice's construction over the box
-    of all K model aabbs, each moved by its pose (block -> scene; None: the aabb as given).  h = the box's longest extent / resolution, origin =
-    lo - h, n_k = ceil(ext_k / h) + 3 nodes, the same directed rounding, the same ValueErrors.  scene_lattice([s, t], [P, None], r) is
-    pair_lattice(s, t, P, r)."""
+    """(origin, spacing, (nx, ny, nz)) of the lattice a scene is meshed on, in the SCENE frame.  In fp64: the box of all K model aabbs, each moved
+    (its eight corners) by its pose (block -> scene; None: the aabb as given); h = the box's longest extent / resolution (cubic cells); origin =
+    lo - h and n_k = ceil(ext_k / h) + 3 nodes (resolution + 3 on the longest axis), so the first and the last node of every axis lie at least h
+    outside every aabb: the lattice's shell is exactly 0 and every level > 0 gives a closed mesh.  origin and spacing are fp32-exact Python floats;
+    the rounding is directed (h up, after one part in 2^20 is added to it; origin down from lo - h) so that it cannot eat the margin.  ValueError
+    when a dimension exceeds 1024 or the nodes exceed 2^28."""
     if int(resolution) < 1:
         raise ValueError(f"scene_lattice: resolution {resolution} must be >= 1")
     resolution = int(resolution)
@@ -59,8 +108,7 @@ def blend_scene_attributes(weight_block, sigma_block, Rs, grads, colors=None):
     frame, colors a list of K [V,3] or None.  With a_b = omega_b sigma_b: g = sum_b omega_b R_b grad_b (the gradient of the overlap weight is
     ignored), normal = -g / |g| (zeros where g vanishes or is not finite); colour = sum_b a_b c_b / sum_b a_b (one block's own colour, bit for bit,
     where it alone has a_b != 0) and share [V,K] = a_b / sum a, both zeros where the denominator is 0.  All sums run in block order.  Returns
-    (normals, colors or None, share); with K = 2 and Rs = [R, None] this is pair_field.blend_vertex_attributes, bit for bit (share[:,0] =
-    weight_src)."""
+    (normals, colors or None, share); pair_field.blend_vertex_attributes is the call with K = 2 and Rs = [R, None] (share[:,0] = weight_src)."""
     K = weight_block.shape[1]
     g = None
     for b in range(K):
@@ -165,33 +213,19 @@ class SceneField:
     @torch.no_grad()
     def sample_lattice(self, origin, spacing, dims) -> torch.Tensor:
         """The scene density at the nodes origin + (float)i * spacing of an nx x ny x nz lattice: fp32 [nz,ny,nx].  No position tensor is formed."""
-        nx, ny, nz = (int(v) for v in dims)
-        if min(nx, ny, nz) < 2 or max(nx, ny, nz) > MAX_DIM or nx * ny * nz > MAX_NODES:
-            raise ValueError(f"sample_lattice: lattice {nx} x {ny} x {nz}: every dimension must be in [2, 1024] and the nodes at most 2^28")
+        nx, ny, nz = _lattice_dims(dims)
         return self._run(None, nx * ny * nz, origin, spacing, (nx, ny, nz), False)[0].view(nz, ny, nx)
 
     def lattice(self, resolution: int):
         return scene_lattice([f._aabb_host() for f in self.fields], self.poses, resolution)
 
     def covered(self, b: int, x_b: torch.Tensor) -> torch.Tensor:
-        """Own coverage m_b of block b at x_b [N,3] fp32 of THAT block's frame, in torch fp32 elementwise ops: inside the occupancy roi (0 <= u <= 1
-        on all axes) and the cell clamp(floor(u res), 0, res - 1) set.  Not the hot path (tools, composition baseline)."""
-        roi, b8 = self._grids[b]
-        lo = x_b.new_tensor(roi[:3])
-        u = (x_b - lo) / (x_b.new_tensor(roi[3:]) - lo)
-        inside = ((u >= 0) & (u <= 1)).all(dim=1)
-        res = x_b.new_tensor([float(v) for v in b8.shape])
-        ci = torch.minimum(torch.floor(torch.where(inside[:, None], u, torch.zeros_like(u)) * res).clamp(min=0), res - 1).long()
-        return inside & (b8[ci[:, 0], ci[:, 1], ci[:, 2]] != 0)
+        """Own coverage m_b of block b at x_b [N,3] fp32 of THAT block's frame (grid_covered)."""
+        return grid_covered(*self._grids[b], x_b)
 
     def points_to_block(self, b: int, x: torch.Tensor) -> torch.Tensor:
-        """x [N,3] fp32 of the scene frame in block b's frame, by the kernel's own expression in torch fp32 elementwise ops (the same bits); x
-        itself where the block has no pose."""
-        if self.poses[b] is None:
-            return x
-        Rf, tf = self.R[b], self.t[b]
-        d = [x[:, k] - float(tf[k]) for k in range(3)]
-        return torch.stack([(float(Rf[0, k]) * d[0] + float(Rf[1, k]) * d[1]) + float(Rf[2, k]) * d[2] for k in range(3)], dim=1)
+        """x [N,3] fp32 of the scene frame in block b's frame (points_to_frame: the kernel's bits); x itself where the block has no pose."""
+        return x if self.poses[b] is None else points_to_frame(self.R[b], self.t[b], x)
 
 
 @torch.no_grad()

@@ -927,7 +927,8 @@ int dreg_mc_emit(const float* values, int nx, int ny, int nz, float level, const
                  size_t workspace_bytes, float* verts, int* faces, int V, int F, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- a registered pair of blocks as one density field
- * (csrc/pair_field.hip; rule: DESIGN.md §3i) The density of the scene dreg_ngp_render_pair renders, at points of the TARGET frame: a block
+ * (csrc/scene_field.hip; rule: DESIGN.md §3i) The K = 2 form of dreg_scene_density below — the same kernel and launch with blocks {(src, pose),
+ * (tgt, no pose)} and the parts in four separate arrays.  The density of the scene dreg_ngp_render_pair renders, at points of the TARGET frame: a block
  * contributes where its OWN occupancy cell is set, and where both do they share the point by §3e's overlap weight.  Points form: x fp32 [n,3] on
  * the device, origin = spacing = null.  Lattice form: x = null (n is ignored), origin / spacing: 3 fp32 each in HOST memory, node (ix,iy,iz) at
  * origin[c] + (float)i_c * spacing[c] (dreg_mc_emit's position of the node), outputs [nz,ny,nx] with x fastest; no position buffer exists.
@@ -939,7 +940,7 @@ int dreg_mc_emit(const float* values, int nx, int ny, int nz, float level, const
  * sigma = fl(fl(w_src sigma_src) + fl(w_tgt sigma_tgt)).  One launch on `stream`, no atomics, never allocates: identical bytes between runs,
  * point orders and the two forms.  DREG_EINVAL before any launch: a null required pointer, n < 0, both forms at once, a lattice dimension < 2 or
  * > 1024 or more than 2^28 nodes, a power that is not finite and positive, an occupancy-grid dimension <= 0.  Points form with n == 0: DREG_OK,
- * nothing is launched. */
+ * nothing is launched.  Each of the four optional outputs is optional on its own. */
 int dreg_pair_density(const float* x, long n, const float* origin, const float* spacing, int nx, int ny, int nz,
                       const uint8_t* src_binary, int src_rx, int src_ry, int src_rz, const void* src_table, const void* src_w1, const void* src_w2,
                       const uint32_t* src_offset, const uint32_t* src_size, const uint32_t* src_res, const float* src_scale, const uint32_t* src_hashed,

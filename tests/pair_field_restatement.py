@@ -1,4 +1,4 @@
-"""CPU restatement of the pair density field (csrc/pair_field.hip, dreg_nerf_amd/pair_field.py; rule: DESIGN.md §3i) in numpy.  Everything that is a
+"""CPU restatement of the pair density field (dreg_pair_density of csrc/scene_field.hip, dreg_nerf_amd/pair_field.py; rule: DESIGN.md §3i) in numpy.  Everything that is a
 RULE is fp64 here (coverage, weight, blend); the one piece the kernel pins to fp32 bits, the position of a point in the source frame, is restated in
 fp32 numpy ops in the kernel's order.  A block is a dict: roi (6 floats), binary (bool / uint8 [rx,ry,rz]), center (3 floats) and sigma, a
 callable x [N,3] -> density [N] in the block's own frame."""

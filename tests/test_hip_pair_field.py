@@ -1,4 +1,4 @@
-"""GPU: the pair density field (csrc/pair_field.hip, dreg_nerf_amd/pair_field.py; rule: DESIGN.md §3i; restatement: tests/pair_field_restatement.py).
+"""GPU: the pair density field (dreg_pair_density of csrc/scene_field.hip, dreg_nerf_amd/pair_field.py; rule: DESIGN.md §3i; restatement: tests/pair_field_restatement.py).
 
 * The parts are the blocks' own dense queries bit for bit, masked by a torch statement of the coverage rule; the blend is exact given its parts.
 * The overlap weight against the fp64 restatement on the shared points: |dw| <= 5e-6.  With y = 0.5 p ln q, |dw/dy| <= 1/4; taking the native
@@ -8,7 +8,7 @@
 * One block empty: the lattice, the mesh and its attributes are the other block's.
 * Lattice form == points form; permutations permute; two runs give identical bytes.
 * pair_mesh at resolution 24: zero shell, closed, positive volume, unit normals, colours and weight_src in [0,1].
-* Every C guard with sentinels; the Python guards; eval_nerf_regtr.py --merged_mesh_field on a one-scene split on disk."""
+* Every C guard with sentinels; every part output optional on its own, through both entries of the one kernel; the Python guards; eval_nerf_regtr.py --merged_mesh_field on a one-scene split on disk."""
 import ctypes
 import json
 import math
@@ -345,6 +345,58 @@ def test_every_c_guard_returns_einval_without_a_launch(pf, ref):
     assert lat(sigma=L.ptr(small), rest=[None] * 4) == 0
     torch.cuda.synchronize()
     assert _same(small.view(4, 4, 4), pf.sample_lattice([-1.0] * 3, [0.25] * 3, (4, 4, 4)))
+
+
+def test_every_part_output_is_optional_on_its_own(pair, pf, ref):
+    """The per-block part outputs go out through one nullable pointer per block and array.  n = 65 points (one full chunk plus one lane, points of
+    all four coverage classes): with any one part pointer of dreg_pair_density given and the other three null, and with w_tgt + sigma_src alone,
+    the arrays asked for hold the bytes of the all-parts call, the others are untouched and sigma is the same every time; the same for
+    dreg_scene_density at K = 3 with weight_block alone and with sigma_block alone."""
+    from dreg_nerf_amd import scene_field as S
+    lib = L.load()
+    keep = []
+    blocks = [pf._block_args(0, keep), pf._block_args(1, keep)]
+    n, SENT, s = 65, -77.0, L.stream()
+    x = torch.cat([ref["x"][ref["classes"][k]][:17] for k in ("both", "src", "tgt", "none")])[:n].contiguous()
+    assert x.shape == (n, 3)
+
+    def pair_call(asked):
+        outs = [torch.full((n,), SENT, device=DEV) for _ in range(5)]
+        rest = [L.ptr(outs[k]) if k in asked else None for k in range(1, 5)]
+        assert lib.dreg_pair_density(L.ptr(x), n, None, None, 0, 0, 0, *blocks[0], *blocks[1], pf._pose12, pf.power, L.ptr(outs[0]), *rest, s) == 0
+        torch.cuda.synchronize()
+        return outs
+
+    full = pair_call({1, 2, 3, 4})
+    for got, want in zip(full, pf.query(x, parts=True)):
+        assert _same(got, want)
+    assert bool(((full[1] > 0) & (full[1] < 1)).any()) and bool((full[1] == 1).any()) and bool((full[2] == 1).any()) and bool((full[0] == 0).any())
+    for asked in ({1}, {2}, {3}, {4}, {2, 3}):
+        got = pair_call(asked)
+        assert _same(got[0], full[0]), asked
+        for k in range(1, 5):
+            assert _same(got[k], full[k]) if k in asked else bool((got[k] == SENT).all()), (asked, PARTS[k])
+
+    (sf, so), (tf, to) = pair
+    third = torch.eye(4)
+    third[:3, 3] = torch.tensor([0.2, -0.1, 0.15])
+    sc = S.SceneField([(sf, so, C_SRC, POSE), (tf, to, C_TGT, None), (sf, so, C_SRC, third)])
+    arr = sc._block_array(keep)
+
+    def scene_call(want_w, want_s):
+        sigma, wb, sb = torch.full((n,), SENT, device=DEV), torch.full((n, 3), SENT, device=DEV), torch.full((n, 3), SENT, device=DEV)
+        assert lib.dreg_scene_density(L.ptr(x), n, None, None, 0, 0, 0, 3, ctypes.cast(arr, ctypes.c_void_p), sc.power, L.ptr(sigma),
+                                      L.ptr(wb) if want_w else None, L.ptr(sb) if want_s else None, s) == 0
+        torch.cuda.synchronize()
+        return sigma, wb, sb
+
+    full3 = scene_call(True, True)
+    for got, want in zip(full3, sc.query(x, parts=True)):
+        assert _same(got, want)
+    assert bool(((full3[1] > 0).sum(dim=1) == 3).any())                     # some point is shared by all three blocks
+    only_w, only_s = scene_call(True, False), scene_call(False, True)
+    assert _same(only_w[0], full3[0]) and _same(only_w[1], full3[1]) and bool((only_w[2] == SENT).all())
+    assert _same(only_s[0], full3[0]) and _same(only_s[2], full3[2]) and bool((only_s[1] == SENT).all())
 
 
 def test_python_guards(pair, pf):

@@ -267,6 +267,27 @@ def test_scene_attribute_blend_of_two_blocks_is_the_pair_blend_bit_for_bit():
     assert int(((got[2][:, 0] > 0) & (got[2][:, 0] < 1)).sum()) > 200
 
 
+def test_scene_attribute_blend_of_two_blocks_is_the_pair_blend_on_empty_and_nan_rows():
+    """rows: 0 a_T = 0 | 1 a_S = 0 | 2 both a = 0 by the weights | 3 both a = 0 by the densities | 4 sigma_S NaN | 5 w_T NaN | 6 shared and finite;
+    under a rotated source, with and without colours: the same bits from both functions, and zeros wherever the denominator is 0 or not a number."""
+    nan = float("nan")
+    ws, wt = torch.tensor([1.0, 0.0, 0.0, 0.5, 0.5, 0.5, 0.25]), torch.tensor([0.0, 1.0, 0.0, 0.5, 0.5, nan, 0.75])
+    ss, st = torch.tensor([3.0, 9.0, 4.0, 0.0, nan, 2.0, 4.0]), torch.tensor([7.0, 2.0, 4.0, 0.0, 2.0, 2.0, 4.0])
+    g = torch.Generator().manual_seed(1)
+    gs, gt = torch.randn(7, 3, generator=g), torch.randn(7, 3, generator=g)
+    cs, ct = torch.rand(7, 3, generator=g), torch.rand(7, 3, generator=g)
+    R = torch.from_numpy(_pose(63.0, axis=0)[:3, :3]).float()
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for colours in (False, True):
+        want = P.blend_vertex_attributes(ws, wt, ss, st, R, gs, gt, cs if colours else None, ct if colours else None)
+        got = S.blend_scene_attributes(torch.stack([ws, wt], dim=1), torch.stack([ss, st], dim=1), [R, None], [gs, gt], [cs, ct] if colours else None)
+        assert torch.equal(bits(got[0]), bits(want[0])) and torch.equal(bits(got[2][:, 0]), bits(want[2]))
+        assert (got[1] is None and want[1] is None) if not colours else torch.equal(bits(got[1]), bits(want[1]))
+    assert torch.equal(want[2], torch.tensor([1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.25])) and (got[2][2:6] == 0).all()
+    assert torch.equal(got[1][0], cs[0]) and torch.equal(got[1][1], ct[1]) and (got[1][2:6] == 0).all() and (got[1][6] > 0).all()
+    assert (got[0][2] == 0).all() and (got[0][5] == 0).all() and torch.isfinite(got[0]).all()
+
+
 # ------------------------------------------------------------------------------------------------------- the evaluator's flag
 def test_scene_mesh_field_flag_parses_and_implies_register_scene(monkeypatch):
     cfg = config_parser([])

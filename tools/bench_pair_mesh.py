@@ -2,7 +2,7 @@
 """Surface mesh of a registered PAIR of generated 128^3 blocks (tools/bench_render.py make_block, seeds 3 and 5, under the pose of
 tests/test_hip_pair_field.py: 25 degrees about z, t = (-0.13, 0.02, 0.02)) on pair_lattice(--resolution 256).
 
-  fused        ms for PairField.sample_lattice: ONE launch of pair_density_kernel over the lattice, no position tensor
+  fused        ms for PairField.sample_lattice: ONE launch of the density-field kernel (dreg_pair_density) over the lattice, no position tensor
   composition  ms for the same lattice from the calls the tree had before the fused kernel: node positions in torch, the source-frame positions,
                two query_raw, the two coverage masks, the weight and the blend as torch elementwise ops (in z-slabs of mesh.QUERY_CHUNK nodes, as
                mesh.sample_density_lattice walks a block's lattice).  The baseline the fused kernel is judged against; its result is compared

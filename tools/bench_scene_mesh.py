@@ -8,7 +8,6 @@ scene_lattice(--resolution 256).  Per K:
                the K coverage masks, the K (K - 1) weight terms and the blend as torch elementwise ops (in z-slabs of mesh.QUERY_CHUNK nodes).
                Its result is compared with the fused one (bit for bit where at most one block covers a node, the shared nodes to the weights'
                accuracy).
-  pair         (K = 2) ms for PairField.sample_lattice of the same two blocks on the same lattice: the same bytes from the pair kernel
   count, emit  ms for dreg_mc_count and dreg_mc_emit on the fused lattice; V and F
   skipped      per block, the share of the lattice's 64-node waves in which no lane is covered by it (that block's phase is skipped)
 
@@ -28,7 +27,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from dreg_nerf_amd import lib as L  # noqa: E402
 from dreg_nerf_amd import mesh  # noqa: E402
-from dreg_nerf_amd import pair_field as P  # noqa: E402
 from dreg_nerf_amd import scene_field as S  # noqa: E402
 from bench_pair_mesh import event_ms, skipped_share  # noqa: E402
 
@@ -132,11 +130,6 @@ def main():
                                      V, F, L.stream()), "dreg_mc_emit")
 
         steps = {"fused": lambda: sf.sample_lattice(origin, spacing, dims), "composition": lambda: composition(sf, origin, spacing, dims), "count": count, "emit": emit}
-        if K == 2:
-            pf = P.PairField(made[0][0], made[0][1], made[1][0], made[1][1], Pk[0], centers[0], centers[1])
-            assert pf.lattice(args.resolution) == (origin, spacing, dims)
-            agree["bit_equal_to_pair_kernel"] = bool(torch.equal(values.view(torch.int32), pf.sample_lattice(origin, spacing, dims).view(torch.int32)))
-            steps["pair"] = lambda: pf.sample_lattice(origin, spacing, dims)
         for _ in range(args.warmup):
             for fn in steps.values():
                 fn()
@@ -151,8 +144,6 @@ def main():
         row = {"dims": list(dims), "nodes": nodes, "V": V, "F": F, "area": area, "volume": vol,
                "ms": {k: {"median": med[k], "min": min(v), "max": max(v)} for k, v in times.items()},
                "composition_over_fused": med["composition"] / med["fused"], "waves_skipped_share": skipped, "fused_vs_composition": agree}
-        if K == 2:
-            row["fused_over_pair"] = med["fused"] / med["pair"]
         res["scenes"][f"K{K}"] = row
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
