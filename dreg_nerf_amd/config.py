@@ -105,6 +105,12 @@ def config_parser(argv=None):
                    help="eval_nerf_regtr.py: implies --register_scene; then, per scene whose block checkpoints are on disk, mesh ALL its blocks as ONE density field "
                         "(fused K-block density kernel, DESIGN.md 3k; --mesh_resolution cells on the scene's longest axis, --mesh_level) under the ground-truth "
                         "and the synchronised poses: scene_field_mesh_gt.ply, scene_field_mesh_aligned.ply and scene_field_mesh.json (K; V, F, area, volume of both)")
+    p.add_argument("--scene_voxel_grid", action="store_true",
+                   help="eval_nerf_regtr.py: implies --register_scene; then, per scene whose block checkpoints are on disk, extract ALL its blocks as ONE voxel grid "
+                        "(fused K-block radiance kernel, DESIGN.md 3l; --scene_grid_resolution cells per axis over the scene's box) under the ground-truth and the "
+                        "synchronised poses: scene_voxel_grid_{gt,aligned}.pt, scene_voxel_mask_{gt,aligned}.pt (the format of a block's voxel_grid.pt / "
+                        "voxel_mask.pt), the kept samples as .ply and scene_voxel_grid.json (K, resolution, box, kept cells, IoU of the two kept sets)")
+    p.add_argument("--scene_grid_resolution", type=int, default=128, help="--scene_voxel_grid: cells per axis of the merged voxel grid")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

@@ -10,22 +10,8 @@
 // interpolation in fp32 rounded to fp16, layer inputs fp16, accumulation fp32 (tcnn accumulates in fp16 — unpinned).
 // The 18 viewing directions are constants of the caller, so the SH half of the colour net's first layer collapses to one
 // bias vector per direction (c_k = W1[:, :16] sh_k, computed by the caller) and the geometry half is computed once per point.
-#include "ngp_field.h"    // NgpLevels, the hash-grid level gather, the density MLP, wave_sync, store_relu4: shared with the ray marchers (march.h)
-
-// The same with the ReLU on the packed-half VALU: round the four sums to fp16 first (round-to-nearest, as the plain cast), then ONE
-// v_pk_max_f16 per pair — relu(rn(x)) == rn(relu(x)), so the stored bits are those of store_relu4.  (The library is built without
-// packed-fp32 VALU instructions; packed fp16 ones are not affected: DESIGN.md, co-execution fault.)
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void store_relu4_pk(char* sH, int row_stride, int point, int hidden, const f32x4_t& v)
-{
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
-    f16x2_t a = {(_Float16)v[0], (_Float16)v[1]}, b = {(_Float16)v[2], (_Float16)v[3]};
-    a = __builtin_elementwise_max(a, z);
-    b = __builtin_elementwise_max(b, z);
-    const f16x4_t h = {a[0], a[1], b[0], b[1]};
-    *reinterpret_cast<f16x4_t*>(sH + point * row_stride + hidden * 2) = h;
-}
+#include "ngp_field.h"    // NgpLevels, the hash-grid level gather, the density MLP, wave_sync, store_relu4 / store_relu4_pk: shared with the ray
+                          // marchers (march.h) and the scene kernels (scene_field.h)
 
 // ------------------------------------------------------------------------------------------------ density
 // x world [Np,3] fp32 -> density fp32 [Np] (= exp(h0 - 1) * inside), raw fp16 [Np,16] (h0 | 15 geometry features)
@@ -281,6 +267,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 //  * the direction's bias joins on the matrix pipe (hi + lo halves against a ones operand: packed by ngp_dir_bias_kernel), ReLU on the
 //    packed-half VALU, the sigmoid on dense lanes (lane = (point, channel) of the chunk): ~50 VALU per chunk and direction.
 // biaspk: uint32 [ndir][64] = fp16 (hi | lo << 16) of c_k[j];  same sums in the same order as ngp_rgb_kernel up to the bias split (2^-22).
+// The per-tile body (from the first-layer product to the direction loop's end) is ALSO stated as ngp_rgb_tile in ngp_field.h, which the merged
+// voxel grid (scene_grid.hip) calls.  This kernel keeps its body written out: through the function it took 120 instead of 118 VGPRs.  The
+// arithmetic is the same; tests/test_hip_scene_grid.py holds the two to the same bits.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void ngp_rgb_chunks_kernel(
     const _Float16* __restrict__ raw, const _Float16* __restrict__ w1, const _Float16* __restrict__ w2, const _Float16* __restrict__ w3,
     const uint32_t* __restrict__ biaspk, float* __restrict__ rgb, int ndir, int Np)

@@ -48,6 +48,21 @@ __device__ __forceinline__ void store_relu4(char* sH, int row_stride, int point,
     *reinterpret_cast<f16x4_t*>(sH + point * row_stride + hidden * 2) = h;
 }
 
+// The same with the ReLU on the packed-half VALU: round the four sums to fp16 first (round-to-nearest, as the plain cast), then ONE
+// v_pk_max_f16 per pair — relu(rn(x)) == rn(relu(x)), so the stored bits are those of store_relu4.  (The library is built without
+// packed-fp32 VALU instructions; packed fp16 ones are not affected: DESIGN.md, co-execution fault.)
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_relu4_pk(char* sH, int row_stride, int point, int hidden, const f32x4_t& v)
+{
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+    const f16x2_t z = {(_Float16)0.f, (_Float16)0.f};
+    f16x2_t a = {(_Float16)v[0], (_Float16)v[1]}, b = {(_Float16)v[2], (_Float16)v[3]};
+    a = __builtin_elementwise_max(a, z);
+    b = __builtin_elementwise_max(b, z);
+    const f16x4_t h = {a[0], a[1], b[0], b[1]};
+    *reinterpret_cast<f16x4_t*>(sH + point * row_stride + hidden * 2) = h;
+}
+
 // ------------------------------------------------------------------------------------------------ unit coordinates
 // Unit-cube coordinates u (clamped to [0,1]) of the world position x in the aabb (lo, hi), and whether x lies strictly inside
 // (ngp.py:157-167; outside, the callers set the density to 0).
@@ -155,4 +170,81 @@ __device__ __forceinline__ void ngp_density_mlp(const NgpDensityW& w, const char
         for (int kb = 0; kb < 2; ++kb) ov = __builtin_amdgcn_mfma_f32_16x16x32_f16(ldsfrag(sH, NGP_HRS, rb * 16 + fr, kb * 32 + kg * 8), w.w2f[kb], ov, 0, 0, 0);
         epi(rb, ov);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ colour MLP, shared directions, 16-point tiles
+// The colour net's weights as MFMA operands, held in registers across tiles and directions: w1 fp16 [64][32], w2 fp16 [64][64], w3 fp16 [16][64].
+struct NgpColorW { f16x8_t w1f[4], w2f[4][2], w3f[2]; };
+__device__ __forceinline__ void ngp_load_color_w(NgpColorW& w, const _Float16* w1, const _Float16* w2, const _Float16* w3, int lane)
+{
+    const int fr = lane & 15, kg = lane >> 4;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        w.w1f[cb] = *reinterpret_cast<const f16x8_t*>(w1 + (cb * 16 + fr) * 32 + kg * 8);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) w.w2f[cb][kb] = *reinterpret_cast<const f16x8_t*>(w2 + (cb * 16 + fr) * 64 + kb * 32 + kg * 8);
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) w.w3f[kb] = *reinterpret_cast<const f16x8_t*>(w3 + fr * 64 + kb * 32 + kg * 8);
+}
+
+// The per-tile body of the chunked colour kernel (ngp_rgb_chunks_kernel of ngp.hip; the merged voxel grid of scene_grid.hip calls it too, so
+// the two agree bit for bit by construction).  On entry the first 16 rows of sH (stride NGP_XRS) hold X = (0 x16 | feat[1..15] | 1) of the
+// tile's 16 points, written by this wave; sH is one 16 x 64 fp16 tile (stride NGP_HRS), sO 16 x 4 floats.  ones: 1 in K columns 0 and 1 of the
+// kg == 0 lanes, 0 elsewhere; biaspk: uint32 [ndir][64] = fp16 (hi | lo << 16) of the direction's bias c_k[j] (ngp_dir_bias_kernel).  Returns,
+// in lanes 0..47 = (point lane / 3, channel lane % 3), the SUM over the directions of fp16(sigmoid(fp16(pre-activation))); the caller scales by
+// 1 / ndir.  A point's row depends on that row alone.  The caller's wave_sync() follows before the tile or sO is rewritten.
+__device__ __forceinline__ float ngp_rgb_tile(const NgpColorW& w, const f16x8_t& ones, const uint32_t* __restrict__ biaspk, int ndir, char* sH, float* sO, int lane)
+{
+    constexpr int XRS = NGP_XRS, HRS = NGP_HRS;
+    const int fr = lane & 15, kg = lane >> 4;
+    const int opt = lane / 3, och = lane - opt * 3;                  // dense output role: lanes 0..47 = (point, channel) of the tile
+    wave_sync();
+    f32x4_t base[4];
+    {
+        const f16x8_t af = ldsfrag(sH, XRS, fr, kg * 8);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) base[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.w1f[cb], af, (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    }
+    float sum = 0.f;
+#pragma unroll 1
+    for (int k = 0; k < ndir; ++k) {
+        f16x8_t bfr[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const uint32_t pk = kg == 0 ? biaspk[k * 64 + cb * 16 + fr] : 0u;
+            typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+            bfr[cb] = __builtin_bit_cast(f16x8_t, (u32x4_t){pk, 0u, 0u, 0u});
+        }
+        wave_sync();
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+            store_relu4_pk(sH, HRS, fr, cb * 16 + kg * 4, __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[cb], ones, base[cb], 0, 0, 0));
+        wave_sync();
+        f16x8_t af[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) af[kb] = ldsfrag(sH, HRS, fr, kb * 32 + kg * 8);
+        f32x4_t h[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            h[cb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) h[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.w2f[cb][kb], af[kb], h[cb], 0, 0, 0);
+        }
+        wave_sync();                                  // every lane has read its layer-1 fragments: the tile may be overwritten
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) store_relu4_pk(sH, HRS, fr, cb * 16 + kg * 4, h[cb]);
+        wave_sync();
+        f32x4_t o = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) o = __builtin_amdgcn_mfma_f32_16x16x32_f16(ldsfrag(sH, HRS, fr, kb * 32 + kg * 8), w.w3f[kb], o, 0, 0, 0);
+        if (fr < 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sO[(kg * 4 + r) * 4 + fr] = o[r];
+        }
+        wave_sync();
+        const float hv = (float)(_Float16)sO[(lane < 48 ? opt : 0) * 4 + och];
+        sum += (float)(_Float16)__builtin_amdgcn_rcpf(1.f + __expf(-hv));
+    }
+    return sum;
 }

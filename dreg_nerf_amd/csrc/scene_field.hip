@@ -35,16 +35,7 @@
 // block and array and one stride: [n,K] rows for the scene entry, four separate [n] arrays for the pair entry.  No atomics, no process-global
 // state; a point's result depends on nothing but the point, so the output is bit-identical between runs, launch widths, orders and forms.  As
 // built: DESIGN.md §3k.
-#include "march.h"
-#include "../../include/dreg_nerf.h"   // dreg_field_block, DREG_SCENE_MAX_BLOCKS and the signature check of the entry point defined here
-
-#define FIELD_MAXB DREG_SCENE_MAX_BLOCKS
-
-struct SceneFieldBlock : MarchBlock {
-    float center[3];            // centroid of the block's cameras, in the block's frame
-    float R[9], t[3];           // the pose rounded to fp32: R row-major, then t (block -> scene); unused without a pose
-    int has_pose;
-};
+#include "scene_field.h"   // SceneFieldBlock, its fill, the coverage and the weights: shared with the merged voxel grid (scene_grid.hip)
 
 struct SceneFieldArgs {
     SceneFieldBlock b[FIELD_MAXB];      // the first K are filled, the rest zero
@@ -63,27 +54,6 @@ struct SceneFieldArgs {
 static_assert(sizeof(SceneFieldArgs) <= 4096, "the blocks are read from the kernel-argument segment");
 
 static constexpr long SCENE_FIELD_WAVES = 16384;    // one-wave workgroups of the launch at most (256 CUs x 16 resident x 4 rounds)
-
-// the scene-frame point x in block b's frame
-__device__ __forceinline__ void scene_field_to_block(const SceneFieldBlock& b, const float (&x)[3], float (&xb)[3])
-{
-    if (b.has_pose) {
-        const float d[3] = {x[0] - b.t[0], x[1] - b.t[1], x[2] - b.t[2]};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xb[k] = (b.R[k] * d[0] + b.R[3 + k] * d[1]) + b.R[6 + k] * d[2];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xb[k] = x[k];
-    }
-}
-
-// whether block b's own occupancy grid covers the point x of its frame (the extents as march_grid forms them: the same fp32 subtraction)
-__device__ __forceinline__ bool scene_field_covered(const MarchBlock& b, const float (&x)[3])
-{
-    const int rdim[3] = {b.rx, b.ry, b.rz};
-    const float ext[3] = {b.roi[3] - b.roi[0], b.roi[4] - b.roi[1], b.roi[5] - b.roi[2]};
-    return march_covered(b.roi, ext, rdim, b.binary, x);
-}
 
 // four waves per SIMD, the residency the 9.25 KB of LDS per wave admit (16 workgroups per CU): without the attribute the two-block form of this
 // kernel took 79 VGPRs + 64 AGPRs, three waves per SIMD; the gathers of a phase are latency, which occupancy hides
@@ -119,54 +89,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
             for (int k = 0; k < 3; ++k) xw[k] = a.origin[k] + (float)ic[k] * a.spacing[k];
         }
-        // ---- every block's own coverage (a bit per block) and the point's squared distance to the block's camera centroid
-        unsigned mask = 0;
-        float del[FIELD_MAXB] = {1.f, 1.f, 1.f, 1.f};
-#pragma unroll 1
-        for (int q = 0; q < K; ++q) {
-            const SceneFieldBlock& b = a.b[q];
-            float xb[3];
-            scene_field_to_block(b, xw, xb);
-            const bool m = valid && scene_field_covered(b, xb);
-            float d = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { const float e = xb[k] - b.center[k]; d += e * e; }
-            d += 1e-12f;
-            if (m) mask |= 1u << q;
-#pragma unroll
-            for (int j = 0; j < FIELD_MAXB; ++j) del[j] = (j == q) ? d : del[j];
-        }
-        // ---- the overlap weights (render_scene.hip's arithmetic; the distances are in registers: nothing is read per block)
-        float om[FIELD_MAXB];
-#pragma unroll
-        for (int j = 0; j < FIELD_MAXB; ++j) {
-            float w = 0.f;
-            if ((mask >> j) & 1u) {
-                const unsigned others = mask & ~(1u << j);
-                w = 1.f;
-                if (others != 0) {
-                    if (__popc(others) == 1 && others < (1u << j)) {            // the one other block has the lower index: the pair's omega_hi = 1 - omega_lo
-                        float d_lo = 1.f;
-#pragma unroll
-                        for (int i = 0; i < FIELD_MAXB; ++i) d_lo = ((others >> i) & 1u) ? del[i] : d_lo;
-                        w = 1.f - 1.f / (1.f + __expf(a.half_power * __logf(d_lo / del[j])));
-                    } else {
-                        float sum = 0.f;
-#pragma unroll
-                        for (int i = 0; i < FIELD_MAXB; ++i)
-                            if (i != j && ((others >> i) & 1u)) sum += __expf(a.half_power * __logf(del[j] / del[i]));
-                        w = 1.f / (1.f + sum);
-                    }
-                }
-            }
-            om[j] = w;
-        }
+        // ---- every block's own coverage (a bit per block), the point's squared distance to the block's camera centroid, the overlap weights
+        unsigned mask;
+        float del[FIELD_MAXB], om[FIELD_MAXB];
+        scene_field_coverage(a.b, K, valid, xw, mask, del);
+        scene_field_weights(mask, del, a.half_power, om);
         // ---- each block's density where that block covers the point; one body serves all blocks (the block's arguments are read per phase)
         float sig[FIELD_MAXB] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int q = 0; q < K; ++q) {
             const bool have = (mask >> q) & 1u;
             if (!__any(have)) continue;
+            // (the phase is ALSO stated as scene_field_density in scene_field.h, which scene_grid.hip calls; this kernel keeps its body written
+            // out: through the function it took 119 instead of 117 VGPRs.  tests/test_hip_scene_grid.py holds the two to the same bits.)
             const SceneFieldBlock& b = a.b[q];
             float xb[3], u[3];
             scene_field_to_block(b, xw, xb);
@@ -201,18 +136,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
     }
-}
-
-static int scene_field_fill(SceneFieldBlock& b, const dreg_field_block& h)
-{
-    if (!h.center) return DREG_EINVAL;
-    for (int k = 0; k < 3; ++k) b.center[k] = h.center[k];
-    b.has_pose = h.pose != nullptr;
-    for (int k = 0; k < 9; ++k) b.R[k] = h.pose ? h.pose[k] : 0.f;
-    for (int k = 0; k < 3; ++k) b.t[k] = h.pose ? h.pose[9 + k] : 0.f;
-    // no ray is marched: no colour net, no scene interval (the roi stands in for the scene aabb, the step for a positive number)
-    return march_fill_block(b, h.binary, h.rx, h.ry, h.rz, nullptr, h.table, h.w1, h.w2, false, nullptr, nullptr, nullptr, h.offset, h.size, h.res, h.scale,
-                            h.hashed, h.roi_aabb, h.roi_aabb, h.model_aabb, 0.f, 0.f, 1.f, 0.f, false);
 }
 
 // The ONE launch behind both entry points, and the one statement of the forms, the lattice limits, the chunk counts and the launch width.

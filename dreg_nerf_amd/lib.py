@@ -281,6 +281,8 @@ SIGNATURES = {
     "dreg_pair_density": (I, [P, ctypes.c_long, P, P, I, I, I] + ([P, I, I, I] + [P] * 3 + [P] * 5 + [P] * 3) * 2 + [P, F] + [P] * 5 + [P]),
     # scene_field.hip: x, n, origin, spacing, nx, ny, nz, n_blocks, blocks (HOST array of FieldBlock), power, sigma, weight_block, sigma_block, stream
     "dreg_scene_density": (I, [P, ctypes.c_long, P, P, I, I, I, I, P, F, P, P, P, P]),
+    # scene_grid.hip: rx, ry, rz, grid_aabb, jitter, n_blocks, blocks (HOST array of RadianceBlock), power, delta, density_thre, voxel_grid, keep, sigma, stream
+    "dreg_scene_voxel_grid": (I, [I, I, I, P, P, I, P, F, F, F, P, P, P, P]),
 }
 
 
@@ -322,6 +324,8 @@ PROBE_SIGNATURES = {
     "dreg_render_pair_set_waves": (None, [I]),
     "dreg_render_bwd_set_waves": (None, [I]),
     "dreg_render_scene_set_waves": (None, [I]),
+    "dreg_scene_grid_set_waves": (None, [I]),
+    "dreg_scene_grid_set_lanes_z": (None, [I]),
 }
 PROBE_LIB_PATH = os.path.join(_HERE, "libdreg_nerf_hip_probe.so")
 _probe_lib = None
@@ -347,6 +351,11 @@ class FieldBlock(ctypes.Structure):
     """dreg_field_block of include/dreg_nerf.h (one block's arguments of dreg_scene_density)."""
     _fields_ = ([("binary", P), ("rx", c_int), ("ry", c_int), ("rz", c_int)] +
                 [(n, P) for n in ("table", "w1", "w2", "offset", "size", "res", "scale", "hashed", "roi_aabb", "model_aabb", "center", "pose")])
+
+
+class RadianceBlock(ctypes.Structure):
+    """dreg_radiance_block of include/dreg_nerf.h (one block's arguments of dreg_scene_voxel_grid)."""
+    _fields_ = [("field", FieldBlock)] + [(n, P) for n in ("cw1", "cw2", "cw3", "dirbias")]
 
 
 def load_probe():

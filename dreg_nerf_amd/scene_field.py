@@ -61,19 +61,11 @@ def points_to_frame(Rf, tf, x: torch.Tensor) -> torch.Tensor:
     return torch.stack([(float(Rf[0, k]) * d[0] + float(Rf[1, k]) * d[1]) + float(Rf[2, k]) * d[2] for k in range(3)], dim=1)
 
 
-def scene_lattice(aabbs, poses, resolution: int):
-    """(origin, spacing, (nx, ny, nz)) of the lattice a scene is meshed on, in the SCENE frame.  In fp64: the box of all K model aabbs, each moved
-    (its eight corners) by its pose (block -> scene; None: the aabb as given); h = the box's longest extent / resolution (cubic cells); origin =
-    lo - h and n_k = ceil(ext_k / h) + 3 nodes (resolution + 3 on the longest axis), so the first and the last node of every axis lie at least h
-    outside every aabb: the lattice's shell is exactly 0 and every level > 0 gives a closed mesh.  origin and spacing are fp32-exact Python floats;
-    the rounding is directed (h up, after one part in 2^20 is added to it; origin down from lo - h) so that it cannot eat the margin.  ValueError
-    when a dimension exceeds 1024 or the nodes exceed 2^28."""
-    if int(resolution) < 1:
-        raise ValueError(f"scene_lattice: resolution {resolution} must be >= 1")
-    resolution = int(resolution)
+def _scene_box64(aabbs, poses, who: str):
+    """(lo, hi) fp64 of the box of all K model aabbs, each moved (its eight corners) by its pose (block -> scene; None: the aabb as given)."""
     aabbs, poses = list(aabbs), list(poses)
     if len(aabbs) != len(poses) or not 1 <= len(aabbs) <= L.SCENE_MAX_BLOCKS:
-        raise ValueError(f"scene_lattice: {len(aabbs)} aabbs and {len(poses)} poses (1 to {L.SCENE_MAX_BLOCKS} blocks, one pose or None per block)")
+        raise ValueError(f"{who}: {len(aabbs)} aabbs and {len(poses)} poses (1 to {L.SCENE_MAX_BLOCKS} blocks, one pose or None per block)")
     los, his = [], []
     for aabb, pose in zip(aabbs, poses):
         s = np.asarray([float(v) for v in (aabb.tolist() if torch.is_tensor(aabb) else aabb)], dtype=np.float64)
@@ -86,7 +78,31 @@ def scene_lattice(aabbs, poses, resolution: int):
         moved = corners @ P[:, :3].T + P[:, 3]
         los.append(moved.min(axis=0))
         his.append(moved.max(axis=0))
-    lo, hi = np.min(np.stack(los), axis=0), np.max(np.stack(his), axis=0)
+    return np.min(np.stack(los), axis=0), np.max(np.stack(his), axis=0)
+
+
+def scene_box(aabbs, poses):
+    """The box of a registered scene in the SCENE frame, as 6 fp32-exact Python floats (lo | hi): in fp64 the box of all K model aabbs, each moved
+    (its eight corners) by its pose (block -> scene; None: the aabb as given) — the box scene_lattice spans its lattice over —, rounded OUTWARD
+    to fp32 (lo down, hi up).  It is not made cubic.  ValueError when it spans no volume on some axis."""
+    lo, hi = _scene_box64(aabbs, poses, "scene_box")
+    ext = hi - lo
+    if not (np.isfinite(ext).all() and ext.min() > 0):
+        raise ValueError("scene_box: the aabbs span no volume")
+    return [_f32_down(float(v)) for v in lo] + [_f32_up(float(v)) for v in hi]
+
+
+def scene_lattice(aabbs, poses, resolution: int):
+    """(origin, spacing, (nx, ny, nz)) of the lattice a scene is meshed on, in the SCENE frame.  In fp64: the box of all K model aabbs, each moved
+    (its eight corners) by its pose (block -> scene; None: the aabb as given); h = the box's longest extent / resolution (cubic cells); origin =
+    lo - h and n_k = ceil(ext_k / h) + 3 nodes (resolution + 3 on the longest axis), so the first and the last node of every axis lie at least h
+    outside every aabb: the lattice's shell is exactly 0 and every level > 0 gives a closed mesh.  origin and spacing are fp32-exact Python floats;
+    the rounding is directed (h up, after one part in 2^20 is added to it; origin down from lo - h) so that it cannot eat the margin.  ValueError
+    when a dimension exceeds 1024 or the nodes exceed 2^28."""
+    if int(resolution) < 1:
+        raise ValueError(f"scene_lattice: resolution {resolution} must be >= 1")
+    resolution = int(resolution)
+    lo, hi = _scene_box64(aabbs, poses, "scene_lattice")
     ext = hi - lo
     if not (np.isfinite(ext).all() and ext.max() > 0):
         raise ValueError("scene_lattice: the aabbs span no volume")
@@ -146,9 +162,11 @@ class SceneField:
     """The density field of a registered scene: SceneField(blocks, power=4.0) with blocks a list of 1 to 4 (field, grid, center, pose_or_None).
     Grids are render.BlockGrid or ngp.OccupancyGrid; center: the centroid of the block's cameras in its own frame; pose = G_b = [R|t] ([3,4] or
     [4,4]) maps the block's frame to the scene frame, in which the field lives, or None: the block's frame IS the scene's and points reach it
-    untouched.  Each fp64 pose is rounded to fp32 once (self.R[b], self.t[b]: what the kernel receives; None without a pose)."""
+    untouched.  Each fp64 pose is rounded to fp32 once (self.R[b], self.t[b]: what the kernel receives; None without a pose).  metas (optional,
+    one dict per block with 'camera_poses' [N,4,4] and 'render_step_size', optionally 'aabb' and 'alpha_thre': a checkpoint's meta data) is what
+    extract_grid(surface=True) marches the blocks' own cameras with."""
 
-    def __init__(self, blocks, power: float = 4.0):
+    def __init__(self, blocks, power: float = 4.0, metas=None):
         from . import render
         blocks = list(blocks)
         if not 1 <= len(blocks) <= L.SCENE_MAX_BLOCKS:
@@ -172,6 +190,10 @@ class SceneField:
                         for P, R, t in zip(self.poses, self.R, self.t)]
         self.centers = [[float(v) for v in torch.as_tensor(b[2]).reshape(-1).tolist()] for b in blocks]
         self._grids = [render._grid_parts(b[1], dev)[:2] for b in blocks]        # (roi as 6 host floats, uint8 occupancy on the device)
+        if metas is not None and len(metas) != len(blocks):
+            raise ValueError(f"SceneField: {len(metas)} metas for {len(blocks)} blocks")
+        self.metas = None if metas is None else list(metas)
+        self._dirbias = None                                                     # per block, made by the first extract_grid
 
     def _block_array(self, keep: list):
         arr = (L.FieldBlock * self.K)()
@@ -184,6 +206,86 @@ class SceneField:
             for name, v in zip(names, args):
                 setattr(arr[k], name, ctypes.cast(v, ctypes.c_void_p) if isinstance(v, ctypes.Array) else v)
         return arr
+
+    def _radiance_array(self, keep: list):
+        """The HOST array of dreg_radiance_block for dreg_scene_voxel_grid: every block's dreg_field_block, its colour net and the dir-bias buffer of
+        SampleGrid's 18 fixed viewing directions (made once per field: the weights of a SceneField's blocks are taken as frozen)."""
+        from . import ngp
+        if self._dirbias is None:
+            dirs = ngp.SampleGrid._generate_fixed_viewing_directions().to(self.device).float().contiguous()
+            self._dirbias = [f.dir_bias(dirs) for f in self.fields]             # views of the [2 * 18, 64] buffers dreg_ngp_dir_bias wrote
+        fb = self._block_array(keep)
+        arr = (L.RadianceBlock * self.K)()
+        for k, field in enumerate(self.fields):
+            ctypes.memmove(ctypes.addressof(arr[k].field), ctypes.addressof(fb[k]), ctypes.sizeof(L.FieldBlock))
+            arr[k].cw1, arr[k].cw2, arr[k].cw3 = field.color_ptrs()
+            arr[k].dirbias = self._dirbias[k].data_ptr()
+        keep.append(self._dirbias)
+        return arr
+
+    @torch.no_grad()
+    def extract_grid(self, resolution=128, aabb=None, jitter=None, density_thre: float = 0.7, delta: float = 1e-2, surface: bool = False,
+                     cut_off: float = 0.5) -> dict:
+        """The registered scene as ONE voxel grid in the format of a block's voxel_grid.pt / voxel_mask.pt (csrc/scene_grid.hip, one fused launch;
+        rule: DESIGN.md §3l).  resolution: an int or (rx, ry, rz); aabb: the grid's box in the scene frame (6 floats; default scene_box of the
+        blocks); jitter: [rx ry rz, 3] (or [rx,ry,rz,3]) fp32 offsets of the samples within their cells, None = the cell centres.  Returns
+        {"voxel_grid" fp32 [rx,ry,rz,7] = (xyz | rgb | alpha) at kept cells and 0 elsewhere, "keep" bool [rx,ry,rz] (sigma > density_thre),
+        "sigma" fp32 [rx,ry,rz], "voxel_mask" int64 ascending flat indices of the kept cells, "aabb"}.  surface=True (needs metas): a kept cell
+        stays iff, for some block b that covers it, visibility.surface_visibility of the cell's x_b from b's own cameras through b's own field
+        says visible; rows of cells that fail are zeroed and leave the mask.  Occlusion of one block's cameras by another block is ignored."""
+        res = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+        if len(res) != 3 or min(res) < 1 or max(res) > MAX_DIM or res[0] * res[1] * res[2] > MAX_NODES:
+            raise ValueError(f"extract_grid: resolution {resolution}: three dimensions in [1, 1024] and at most 2^28 cells")
+        box = self.box() if aabb is None else [float(np.float32(v)) for v in (aabb.tolist() if torch.is_tensor(aabb) else aabb)]
+        if len(box) != 6 or not all(math.isfinite(v) for v in box) or not all(np.float32(box[3 + k]) - np.float32(box[k]) > 0 for k in range(3)):
+            raise ValueError(f"extract_grid: aabb {box} must be 6 finite floats with a positive extent on every axis")
+        if not (math.isfinite(float(density_thre)) and math.isfinite(float(delta)) and float(delta) > 0.0):
+            raise ValueError(f"extract_grid: density_thre {density_thre} must be finite and delta {delta} finite and positive")
+        if surface and self.metas is None:
+            raise ValueError("extract_grid: surface=True needs the blocks' metas (camera_poses, render_step_size)")
+        n = res[0] * res[1] * res[2]
+        if jitter is not None:
+            if not jitter.is_cuda or jitter.numel() != 3 * n:
+                raise ValueError(f"extract_grid: jitter must be on the GPU with {n} x 3 entries")
+            jitter = jitter.reshape(n, 3).to(self.device).float().contiguous()
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            grid = torch.empty(n, 7, dtype=torch.float32, device=self.device)
+            keep8 = torch.empty(n, dtype=torch.uint8, device=self.device)
+            sigma = torch.empty(n, dtype=torch.float32, device=self.device)
+            alive = []
+            arr = self._radiance_array(alive)
+            L.check(lib.dreg_scene_voxel_grid(res[0], res[1], res[2], L.f6(box), L.ptr(jitter), self.K, ctypes.cast(arr, ctypes.c_void_p), self.power,
+                                              float(delta), float(density_thre), L.ptr(grid), L.ptr(keep8), L.ptr(sigma), L.stream()), "dreg_scene_voxel_grid")
+            keep = keep8.view(torch.bool)
+            if surface:
+                keep = self._surface_keep(grid, keep, cut_off)
+        return {"voxel_grid": grid.view(*res, 7), "keep": keep.view(*res), "sigma": sigma.view(*res), "voxel_mask": torch.nonzero(keep)[:, 0], "aabb": box}
+
+    def _surface_keep(self, grid, keep, cut_off):
+        """extract_grid's surface mask, a composition of the existing marcher: per block b, the kept cells b covers are marched from b's own cameras
+        through b's own field; cells no block sees are zeroed in `grid` (in place).  Returns the new keep [n]."""
+        from . import visibility
+        idx = torch.nonzero(keep)[:, 0]
+        w = grid[idx, :3].contiguous()
+        seen = torch.zeros(idx.shape[0], dtype=torch.bool, device=self.device)
+        for b, (field, meta) in enumerate(zip(self.fields, self.metas)):
+            xb = self.points_to_block(b, w).contiguous()
+            sel = torch.nonzero(self.covered(b, xb))[:, 0]
+            if sel.numel() == 0:
+                continue
+            roi, b8 = self._grids[b]
+            cams = torch.as_tensor(meta["camera_poses"])[..., :3, 3].to(self.device)
+            vis = visibility.surface_visibility(xb[sel].contiguous(), cams, field, b8, roi, meta.get("aabb", roi), meta["render_step_size"], cut_off, 1e-4,
+                                                float(meta.get("alpha_thre") or 0.0))
+            seen[sel] |= vis.view(-1).bool()
+        grid[idx[~seen]] = 0.0
+        out = keep.clone()
+        out[idx[~seen]] = False
+        return out
+
+    def box(self):
+        return scene_box([f._aabb_host() for f in self.fields], self.poses)
 
     def _run(self, x, n, origin, spacing, dims, parts):
         lib = L.load()

@@ -7,7 +7,9 @@ blocks' surface meshes in one frame under both poses, merged_mesh_pred.ply / mer
 merged_field_mesh_pred.ply / merged_field_mesh_gt.ply / merged_field_mesh.json; with --register_scene every scene registered as a
 whole — all ordered pairs of its blocks, pose synchronisation, scene_metrics_<split>.json — and with --render_scene all its blocks rendered as one
 scene under the ground-truth and the synchronised poses; with --scene_mesh_field all its blocks meshed as ONE density field under both
-pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_mesh.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_mesh.json; with --scene_voxel_grid all its blocks
+extracted as ONE voxel grid in a block's own format under both pose sets, scene_voxel_grid_{gt,aligned}.pt / scene_voxel_mask_{gt,aligned}.pt /
+scene_voxel_grid.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -92,7 +94,7 @@ def write_ransac(d, split, rows, ransac_rows, ransac_refined_rows=None, log=prin
 
 
 def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer=None, metrics=None, log=print):
-    """--register_scene [--scene_robust] [--render_scene] [--scene_mesh_field]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
+    """--register_scene [--scene_robust] [--render_scene] [--scene_mesh_field] [--scene_voxel_grid]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
     {scene: row of scene_metrics_{split}.json}.  Runs after the normal pass; get_scene, the forward calls and the synchronisation draw from no
     random stream.  pair_fn / renderer / metrics are scene_reg's injection points (tests)."""
     from dreg_nerf_amd import scene_reg
@@ -121,6 +123,16 @@ def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer
                     f"{scene_dir}/scene_field_mesh_{{aligned,gt}}.ply", flush=True)
             else:
                 log(f"{name}: no NeRF blocks on disk, scene field mesh not written", flush=True)
+        if getattr(cfg, "scene_voxel_grid", False):   # all blocks as ONE voxel grid in a block's own format: again an input of the network
+            paths = [b.get("nerf_path", "") for b in scene]
+            if all(p and os.path.exists(p) for p in paths):
+                from dreg_nerf_amd.scene_grid import registered_scene_grid
+                scene_dir = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", name)
+                st = registered_scene_grid(scene_dir, scene, scene_reg.ground_truth(scene), res["G"], cfg.dataset, dev, cfg.scene_grid_resolution)["stats"]
+                log(f"{name}: scene voxel grid of {st['K']} blocks at {st['resolution']}, kept cells aligned {st['aligned']['kept']} gt {st['gt']['kept']}, "
+                    f"IoU {st['iou']:.4f} -> {scene_dir}/scene_voxel_grid_{{aligned,gt}}.pt", flush=True)
+            else:
+                log(f"{name}: no NeRF blocks on disk, scene voxel grid not written", flush=True)
     return rows
 
 
@@ -148,9 +160,9 @@ def init_distributed(local_rank: int):
 
 
 def implied_flags(cfg):
-    """The flags other flags imply: the scene render and the scene mesh need the synchronised poses, so --render_scene and --scene_mesh_field each
-    imply --register_scene (and its scene_metrics file)."""
-    if cfg.render_scene or cfg.scene_mesh_field:
+    """The flags other flags imply: the scene render, the scene mesh and the scene voxel grid need the synchronised poses, so --render_scene,
+    --scene_mesh_field and --scene_voxel_grid each imply --register_scene (and its scene_metrics file)."""
+    if cfg.render_scene or cfg.scene_mesh_field or getattr(cfg, "scene_voxel_grid", False):
         cfg.register_scene = True
     return cfg
 

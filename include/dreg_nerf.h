@@ -977,6 +977,32 @@ int dreg_scene_density(const float* x, long n, const float* origin, const float*
                        int n_blocks, const dreg_field_block* blocks, float power,
                        float* sigma, float* weight_block, float* sigma_block, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- a registered scene of K blocks as one voxel grid
+ * (csrc/scene_grid.hip; rule: DESIGN.md §3l) The extraction of a block (sample positions, dense query, mean colour over the 18 fixed directions,
+ * alpha / keep, the [X,Y,Z,7] grid) for the scene density of dreg_scene_density, in ONE launch: a registered scene in the format of a block's
+ * voxel_grid.pt / voxel_mask.pt.  The grid has (rx, ry, rz) cells over grid_aabb (6 fp32 in HOST memory, scene frame), flat index
+ * f = (x ry + y) rz + z.  Cell f is sampled at w_k = ((float)c_k + j_k) / (float)r_k * (hi_k - lo_k) + lo_k (dreg_grid_sample_points' fp32
+ * expression) with j = row f of `jitter` (fp32 [rx ry rz, 3] on the device) or 0.5 where jitter is NULL.  sigma at w has the bits of
+ * dreg_scene_density; alpha = clip(1 - exp(-delta sigma), 0, 1) and keep = sigma > density_thre by dreg_ngp_alpha_keep's arithmetic; the colour of
+ * a kept cell is (sum_b fl(a_b c_b)) / (sum_b a_b) with a_b = fl(omega_b sigma_b) and c_b = dreg_ngp_rgb_mean_fwd's mean colour of block b at the
+ * cell's point of b's own frame, both sums from block 0 upwards in fp32; one block alone with a_b != 0: that block's c_b bit for bit; a
+ * denominator or product that is not finite: c_b of the block with the largest a_b (lowest index on a tie); no block with a_b != 0: 0.
+ * dreg_radiance_block = a dreg_field_block plus the block's colour net (cw1 fp16 [64][32], cw2 fp16 [64][64], cw3 fp16 [16][64]) and `dirbias`,
+ * the buffer dreg_ngp_dir_bias wrote for the 18 directions (2 * 18 * 64 words); `blocks` is a HOST array of n_blocks of them, read before the
+ * call returns.  Outputs on the device: voxel_grid fp32 [rx ry rz, 7] = (w | rgb | alpha) at kept cells and exactly 0 at all others (every row
+ * is written: no fill is needed), keep uint8 [rx ry rz], optional sigma fp32 [rx ry rz] (NULL: not written).  One launch on `stream`, no
+ * atomics, never allocates: identical bytes between runs.  DREG_EINVAL before any launch: a null required pointer (grid_aabb, blocks,
+ * voxel_grid, keep, any pointer of a block other than its pose), n_blocks outside 1..DREG_SCENE_MAX_BLOCKS, a dimension < 1 or > 1024 or more
+ * than 2^28 cells, a box with a non-positive or non-finite extent, power / delta not finite and positive, density_thre not finite, an
+ * occupancy-grid dimension <= 0. */
+typedef struct dreg_radiance_block {
+    dreg_field_block field;
+    const void *cw1, *cw2, *cw3;
+    const float* dirbias;
+} dreg_radiance_block;
+int dreg_scene_voxel_grid(int rx, int ry, int rz, const float* grid_aabb, const float* jitter, int n_blocks, const dreg_radiance_block* blocks,
+                          float power, float delta, float density_thre, float* voxel_grid, uint8_t* keep, float* sigma, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- active-set 3^3 convolution with
  * staged-neighbourhood reuse (csrc/conv_brick.hip): the FPN head layers upsample_transform_{1,2} / pyramid_transformation_1 and their
  * data gradients on the voxels around the occupied surface (conerf/model/feature_pyramid_net.py:47-56,97-103; the reference runs
