@@ -111,6 +111,12 @@ def config_parser(argv=None):
                         "synchronised poses: scene_voxel_grid_{gt,aligned}.pt, scene_voxel_mask_{gt,aligned}.pt (the format of a block's voxel_grid.pt / "
                         "voxel_mask.pt), the kept samples as .ply and scene_voxel_grid.json (K, resolution, box, kept cells, IoU of the two kept sets)")
     p.add_argument("--scene_grid_resolution", type=int, default=128, help="--scene_voxel_grid: cells per axis of the merged voxel grid")
+    p.add_argument("--merge_scene", action="store_true",
+                   help="eval_nerf_regtr.py: implies --register_scene; then, per scene whose block checkpoints are on disk, distil ALL its blocks into ONE NeRF "
+                        "block per pose set (field distillation on points, DESIGN.md 3m): merged_block_{gt,aligned}/model.pth in the format of a "
+                        "train_ngp_nerf.py checkpoint, and merged_block.json (K, steps, points, final loss, PSNR / SSIM against the K-block render)")
+    p.add_argument("--merge_iterations", type=int, default=2000, help="--merge_scene: distillation steps (untuned)")
+    p.add_argument("--merge_points", type=int, default=65536, help="--merge_scene: points per distillation step (untuned)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

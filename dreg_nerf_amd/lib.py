@@ -260,6 +260,9 @@ SIGNATURES = {
     "dreg_ngp_render_bwd_workspace_bytes": (Z, [ctypes.c_long]),
     "dreg_ngp_render_bwd": (I, [P, P, P, ctypes.c_long, P, I, I, I, P, P, P] + [P] * 5 + [P, P, P] + [F] * 5 + [P, P, P, P, P, Z, P]),
     "dreg_ngp_adam_step": (I, [P] * 5 + [Z, F, F, F, F, I, P]),
+    # field_train.hip: x, dirs, n, base16, color16, the level table, model_aabb, g_sigma, g_rgb, grad_base, grad_color, workspace, bytes, stream
+    "dreg_ngp_points_bwd_workspace_bytes": (Z, [ctypes.c_long]),
+    "dreg_ngp_points_bwd": (I, [P, P, ctypes.c_long, P, P] + [P] * 5 + [P, P, P, P, P, P, Z, P]),
     # image_metrics.hip
     "dreg_image_metrics_workspace_bytes": (Z, [I, I, I, I]),
     "dreg_image_metrics": (I, [P, P, I, I, I, I, P] + [P] * 6 + [P, Z, P]),
@@ -324,6 +327,7 @@ PROBE_SIGNATURES = {
     "dreg_render_pair_set_waves": (None, [I]),
     "dreg_render_bwd_set_waves": (None, [I]),
     "dreg_render_scene_set_waves": (None, [I]),
+    "dreg_points_bwd_set_waves": (None, [I]),
     "dreg_scene_grid_set_waves": (None, [I]),
     "dreg_scene_grid_set_lanes_z": (None, [I]),
 }

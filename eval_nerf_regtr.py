@@ -9,7 +9,8 @@ whole — all ordered pairs of its blocks, pose synchronisation, scene_metrics_<
 scene under the ground-truth and the synchronised poses; with --scene_mesh_field all its blocks meshed as ONE density field under both
 pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_mesh.json; with --scene_voxel_grid all its blocks
 extracted as ONE voxel grid in a block's own format under both pose sets, scene_voxel_grid_{gt,aligned}.pt / scene_voxel_mask_{gt,aligned}.pt /
-scene_voxel_grid.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+scene_voxel_grid.json; with --merge_scene all its blocks distilled into ONE NeRF block under both pose sets,
+merged_block_{gt,aligned}/model.pth / merged_block.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -133,6 +134,16 @@ def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer
                     f"IoU {st['iou']:.4f} -> {scene_dir}/scene_voxel_grid_{{aligned,gt}}.pt", flush=True)
             else:
                 log(f"{name}: no NeRF blocks on disk, scene voxel grid not written", flush=True)
+        if getattr(cfg, "merge_scene", False):   # all blocks distilled into ONE NeRF block: a model.pth every single-block consumer accepts
+            paths = [b.get("nerf_path", "") for b in scene]
+            if all(p and os.path.exists(p) for p in paths):
+                from dreg_nerf_amd.scene_merge import merge_registered_scene
+                scene_dir = os.path.join(cfg.root_dir, "eval", cfg.expname, cfg.dataset or "synthetic", name)
+                st = merge_registered_scene(scene_dir, scene, scene_reg.ground_truth(scene), res["G"], cfg.dataset, dev, cfg.merge_iterations, cfg.merge_points)["stats"]
+                log(f"{name}: {st['K']} blocks merged into one in {st['steps']} steps of {st['points']} points, final loss aligned {st['aligned']['final_loss']:.5f} "
+                    f"gt {st['gt']['final_loss']:.5f} -> {scene_dir}/merged_block_{{aligned,gt}}/model.pth", flush=True)
+            else:
+                log(f"{name}: no NeRF blocks on disk, scene not merged", flush=True)
     return rows
 
 
@@ -161,8 +172,8 @@ def init_distributed(local_rank: int):
 
 def implied_flags(cfg):
     """The flags other flags imply: the scene render, the scene mesh and the scene voxel grid need the synchronised poses, so --render_scene,
-    --scene_mesh_field and --scene_voxel_grid each imply --register_scene (and its scene_metrics file)."""
-    if cfg.render_scene or cfg.scene_mesh_field or getattr(cfg, "scene_voxel_grid", False):
+    --scene_mesh_field, --scene_voxel_grid and --merge_scene each imply --register_scene (and its scene_metrics file)."""
+    if cfg.render_scene or cfg.scene_mesh_field or getattr(cfg, "scene_voxel_grid", False) or getattr(cfg, "merge_scene", False):
         cfg.register_scene = True
     return cfg
 

@@ -845,6 +845,22 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
                         const float* rgb, const float* grad_rgb, float* grad_base, float* grad_color, void* workspace, size_t workspace_bytes, void* stream);
 int dreg_ngp_adam_step(float* p, float* g, float* m, float* v, void* p16, size_t n, float lr, float beta1, float beta2, float eps, int step, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- training of a NeRF block's field on points
+ * (csrc/field_train.hip; rule: DESIGN.md §3m).  dreg_ngp_points_bwd: the backward of the inference forward at n points (x fp32 [n,3] in the
+ * field's frame, dirs fp32 [n,3] unit directions; the forward = dreg_ngp_density_fwd + dreg_ngp_rgb_dir_fwd, recomputed) for the upstream
+ * gradients g_sigma fp32 [n] = dL/dsigma and g_rgb fp32 [n,3] = dL/drgb; either may be null (zeros), with both null nothing is launched.
+ * base16 / color16 and the level table as dreg_ngp_render_bwd takes them; model_aabb: 6 floats in HOST memory with positive extent (sigma = 0
+ * and dL/dh0 = 0 outside it; the colour gradient does not depend on it).  Gradients are ADDED: grad_base fp32 [numel(mlp_base.params)] (the MLP
+ * part [0,3072) from per-chunk slabs reduced in chunk order: bit-identical between runs and launch widths; the hash table [3072,..) with fp32
+ * atomic adds), grad_color fp32 [7168] (rows 3..15 of W3 get nothing).  Positions and directions get no gradient.  workspace:
+ * dreg_ngp_points_bwd_workspace_bytes(n) bytes of device memory (cleared by the call on `stream`; 0 for n <= 0).  DREG_EINVAL, with nothing
+ * launched or written, for n < 0, a null required pointer, a short workspace or an aabb without extent; n == 0 returns DREG_OK first. */
+size_t dreg_ngp_points_bwd_workspace_bytes(long n);
+int dreg_ngp_points_bwd(const float* x, const float* dirs, long n, const void* base16, const void* color16,
+                        const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                        const float* model_aabb, const float* g_sigma, const float* g_rgb, float* grad_base, float* grad_color,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- image metrics of rendered views
  * (csrc/image_metrics.hip; rule: DESIGN.md §3d) SSIM, MSE and PSNR of the reference's evaluate() (eval_ngp_nerf.py:24-31,214-229,
  * conerf/loss/ssim_torch.py) for N image pairs in one call.  pred, gt: fp32 [N,H,W,C], channel-last, contiguous, device; 1 <= C <= 4,
