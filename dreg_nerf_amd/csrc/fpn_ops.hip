@@ -2245,6 +2245,7 @@ int dreg_maxpool3d_fwd(const void* x, void* y, uint8_t* argmax, int B, int Di, i
 {
     hipStream_t st = (hipStream_t)stream;
     const int G = dtype == 0 ? 8 : 4;
+    if (C % G) return DREG_EINVAL;          // the kernels move whole granules: a ragged C would leave the last C % G channels of every row unwritten
     const size_t total = (size_t)B * Do * Ho * Wo * (C / G);
     if (dtype == 0) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(nblocks(total)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, argmax, B, Di, Hi, Wi, Do, Ho, Wo, C);
     else hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(nblocks(total)), dim3(256), 0, st, (const float*)x, (float*)y, argmax, B, Di, Hi, Wi, Do, Ho, Wo, C);
@@ -2257,6 +2258,7 @@ int dreg_maxpool3d_bwd_acc(const void* dy, const uint8_t* argmax, void* dx, int 
 {
     hipStream_t st = (hipStream_t)stream;
     const int G = dtype == 0 ? 8 : 4;
+    if (C % G) return DREG_EINVAL;
     const size_t total = (size_t)B * Di * Hi * Wi * (C / G);
     if (dtype == 0) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(nblocks(total)), dim3(256), 0, st, (const bf16_t*)dy, argmax, (bf16_t*)dx, B, Di, Hi, Wi, Do, Ho, Wo, C, accumulate);
     else hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(nblocks(total)), dim3(256), 0, st, (const float*)dy, argmax, (float*)dx, B, Di, Hi, Wi, Do, Ho, Wo, C, accumulate);
@@ -2286,6 +2288,7 @@ int dreg_downsample_sum(const void* g, void* out, int B, int Df, int Hf, int Wf,
 {
     hipStream_t st = (hipStream_t)stream;
     const int G = dtype == 0 ? 8 : 4;
+    if (C % G) return DREG_EINVAL;
     const size_t total = (size_t)B * Dc * Hc * Wc * (C / G);
     if (dtype == 0) hipLaunchKernelGGL(downsample_sum_kernel<bf16_t>, dim3(nblocks(total)), dim3(256), 0, st, (const bf16_t*)g, (bf16_t*)out, B, Df, Hf, Wf, Dc, Hc, Wc, C);
     else hipLaunchKernelGGL(downsample_sum_kernel<float>, dim3(nblocks(total)), dim3(256), 0, st, (const float*)g, (float*)out, B, Df, Hf, Wf, Dc, Hc, Wc, C);
@@ -2351,6 +2354,7 @@ int dreg_trilinear_gather_fwd(const void* p1, const int64_t* idx, const int* pt_
 {
     hipStream_t st = (hipStream_t)stream;
     const int G = dtype == 0 ? 8 : 4;
+    if (C % G) return DREG_EINVAL;
     const size_t total = (size_t)N * (C / G);
     if (N == 0) return DREG_OK;
     if (dtype == 0) {

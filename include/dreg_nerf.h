@@ -299,7 +299,8 @@ int dreg_sparse_stem_fwd(const void* x, const int* rows, int n, const int* rows_
 int dreg_sparse_stem_bwd(const void* x, const void* dp, const uint8_t* argmax, const void* xam, const void* dl, const int* rows_a, int n_a,
                          const int* rows, int n, const float* scale_shift, const float* mean_rstd, void* dx, float* dgamma, float* dbeta, float* coef, float* workspace,
                          int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int relu, int accumulate, void* stream);
-/* nn.MaxPool3d(3, 2, 1) (resnet3d.py:123,161); argmax: uint8 [B,Do,Ho,Wo,C] tap index for the backward pass. */
+/* nn.MaxPool3d(3, 2, 1) (resnet3d.py:123,161); argmax: uint8 [B,Do,Ho,Wo,C] tap index for the backward pass.
+ * C a multiple of the granule (8 bf16, 4 fp32) for the three entries: DREG_EINVAL otherwise. */
 int dreg_maxpool3d_fwd(const void* x, void* y, uint8_t* argmax, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
                        int C, int dtype, void* stream);
 int dreg_maxpool3d_bwd(const void* dy, const uint8_t* argmax, void* dx, int B, int Di, int Hi, int Wi, int Do, int Ho,
@@ -308,7 +309,7 @@ int dreg_maxpool3d_bwd(const void* dy, const uint8_t* argmax, void* dx, int B, i
 int dreg_maxpool3d_bwd_acc(const void* dy, const uint8_t* argmax, void* dx, int B, int Di, int Hi, int Wi, int Do, int Ho,
                            int Wo, int C, int accumulate, int dtype, void* stream);
 
-/* backward of the nearest x2 upsample + crop: out[b,z,y,x,:] = sum of the in-range 2x2x2 children of g */
+/* backward of the nearest x2 upsample + crop: out[b,z,y,x,:] = sum of the in-range 2x2x2 children of g  (C % 8 bf16 / % 4 fp32, both forms) */
 int dreg_downsample_sum(const void* g, void* out, int B, int Df, int Hf, int Wf, int Dc, int Hc, int Wc, int C,
                         int dtype, void* stream);
 /* the same over a list of coarse voxels only (out is left untouched elsewhere; used when the fine gradient lives on an active set) */
@@ -320,7 +321,7 @@ size_t dreg_colsum_workspace_bytes(size_t M, int C);
 int dreg_colsum(const void* g, float* out, float* workspace, size_t M, int C, int accumulate, int dtype, void* stream);
 
 /* F.interpolate(trilinear, align_corners=True) + masked gather fused (nerf_regtr.py:138-147): p1 [B,d,h,w,C],
- * idx int64 [N] = (x*Yr + y)*Zr + z flat fine-grid index, pt_batch int32 [N] grid id; out [N,C]. */
+ * idx int64 [N] = (x*Yr + y)*Zr + z flat fine-grid index, pt_batch int32 [N] grid id; out [N,C].  C % 8 (bf16 p1) / % 4 (fp32). */
 int dreg_trilinear_gather_fwd(const void* p1, const int64_t* idx, const int* pt_batch, void* out, int N, int d, int h,
                               int w, int C, int Zr, int Xr, int Yr, int dtype, int out_f32, void* stream);
 int dreg_trilinear_gather_bwd(const float* dfeat, const int64_t* idx, const int* pt_batch, float* dp1_f32, int N, int d,
