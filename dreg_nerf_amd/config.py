@@ -117,6 +117,10 @@ def config_parser(argv=None):
                         "train_ngp_nerf.py checkpoint, and merged_block.json (K, steps, points, final loss, PSNR / SSIM against the K-block render)")
     p.add_argument("--merge_iterations", type=int, default=2000, help="--merge_scene: distillation steps (untuned)")
     p.add_argument("--merge_points", type=int, default=65536, help="--merge_scene: points per distillation step (untuned)")
+    p.add_argument("--refine_scene", action="store_true",
+                   help="eval_nerf_regtr.py: implies --register_scene; then every scene's synchronised poses are refined JOINTLY by point-to-plane ICP over all "
+                        "ordered block pairs at once (fused K-block kernels, DESIGN.md 3n; --icp_max_dist, --icp_iters, --icp_normals apply): "
+                        "scene_refined_metrics_{split}.json, and the scene products of the same run take the refined poses")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

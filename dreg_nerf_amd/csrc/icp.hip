@@ -7,20 +7,9 @@
 //   icp_solve_kernel  one workgroup: adds the shares in workgroup order, fp64 Cholesky of the 6x6, xi = -A^-1 b, pose <- exp(xi) pose.
 // The pose (fp64 [12]: R row-major, then t) stays on the device.  A run freezes on convergence (status 1), on fewer than 6 correspondences
 // (2) or on a degenerate system (3); from then on both kernels return at once and the stats rows repeat the last one.
-#include "common.h"
+#include "icp_scan.h"
 
-constexpr int ICP_NSUM = 30;      // 21 of J^T J (upper triangle, row-major), 6 of J^T e, sum e^2, sum d^2, count
-constexpr int ICP_BLOCK = 256;
-constexpr int ICP_STATS = 7;      // count, sum e^2, sum d^2, |omega|, |v|, smallest pivot ratio, status
-
-struct IcpGrid { float lo[3]; float cell; int dim[3]; };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
+// one source point's work (transform, cell, 27-cell scan, gate, e, J, the 30 terms) and the reduction: csrc/icp_scan.h
 __global__ __launch_bounds__(ICP_BLOCK) void icp_corr_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tp, const float* __restrict__ tn,
                                                              const int* __restrict__ perm, const int* __restrict__ cell_start, IcpGrid g,
                                                              const double* __restrict__ pose, float max_d2, int it, const int* __restrict__ frozen,
@@ -28,89 +17,18 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_corr_kernel(const float* __rest
 {
     if (it > 0 && *frozen) return;
     __shared__ double sW[ICP_BLOCK / 64][ICP_NSUM];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = (int)blockIdx.x * ICP_BLOCK + tid;
+    const int i = (int)blockIdx.x * ICP_BLOCK + (int)threadIdx.x;
     double s[ICP_NSUM];
 #pragma unroll
     for (int k = 0; k < ICP_NSUM; ++k) s[k] = 0.0;
     if (i < Ns) {
-        float P[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) P[k] = (float)pose[k];
-        const float p0 = src[(size_t)i * 3], p1 = src[(size_t)i * 3 + 1], p2 = src[(size_t)i * 3 + 2];
-        float q[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = ((P[3 * c] * p0 + P[3 * c + 1] * p1) + P[3 * c + 2] * p2) + P[9 + c];
-        // q's cell; outside the grid (a NaN included) there is no target point within a cell's width: no correspondence
-        bool in = true;
-        int ci[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float fc = floorf((q[c] - g.lo[c]) / g.cell);
-            in = in && (fc >= 0.f) && (fc < (float)g.dim[c]);
-            ci[c] = in ? (int)fc : 0;
-        }
-        int best = -1;
-        float bd = __builtin_inff();
-        if (in) {
-            const int x0 = max(ci[0] - 1, 0), x1 = min(ci[0] + 1, g.dim[0] - 1);
-            for (int dz = -1; dz <= 1; ++dz) {
-                const int z = ci[2] + dz;
-                if (z < 0 || z >= g.dim[2]) continue;
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const int y = ci[1] + dy;
-                    if (y < 0 || y >= g.dim[1]) continue;
-                    // the cells x0..x1 of this row are consecutive ids: one range of the sorted points, in ascending cell id
-                    const int c0 = x0 + g.dim[0] * (y + g.dim[1] * z);
-                    const int j1 = cell_start[c0 + (x1 - x0) + 1];
-                    for (int j = cell_start[c0]; j < j1; ++j) {
-                        const float r0 = q[0] - tp[(size_t)j * 3], r1 = q[1] - tp[(size_t)j * 3 + 1], r2 = q[2] - tp[(size_t)j * 3 + 2];
-                        const float d2 = (r0 * r0 + r1 * r1) + r2 * r2;
-                        if (d2 < bd) { bd = d2; best = j; }
-                    }
-                }
-            }
-        }
-        bool ok = best >= 0 && bd <= max_d2;
-        float n[3] = {0.f, 0.f, 0.f}, r[3] = {0.f, 0.f, 0.f};
-        if (ok) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { n[c] = tn[(size_t)best * 3 + c]; r[c] = q[c] - tp[(size_t)best * 3 + c]; }
-            ok = !(n[0] == 0.f && n[1] == 0.f && n[2] == 0.f);
-        }
+        int best;
+        float bd;
+        const bool ok = icp_point(src, i, tp, tn, cell_start, g, pose, max_d2, s, best, bd);
         if (corr) corr[i] = ok ? perm[best] : -1;
         if (dist2) dist2[i] = ok ? bd : __builtin_inff();
-        if (ok) {
-            const float e = (n[0] * r[0] + n[1] * r[1]) + n[2] * r[2];
-            const float Jf[6] = {q[1] * n[2] - q[2] * n[1], q[2] * n[0] - q[0] * n[2], q[0] * n[1] - q[1] * n[0], n[0], n[1], n[2]};
-            double J[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) J[a] = (double)Jf[a];
-            const double ed = (double)e;
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) s[k++] = J[a] * J[b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] = J[a] * ed;
-            s[27] = ed * ed; s[28] = (double)bd; s[29] = 1.0;
-        }
     }
-    // fixed order: butterfly within the wave (every lane ends with the same sum), then the waves in order
-#pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) s[k] = wave_sum_f64(s[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < ICP_NSUM; ++k) sW[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (tid < ICP_NSUM) {
-        double a = sW[0][tid];
-#pragma unroll
-        for (int w = 1; w < ICP_BLOCK / 64; ++w) a += sW[w][tid];
-        partial[(size_t)blockIdx.x * ICP_NSUM + tid] = a;
-    }
+    icp_block_reduce(s, sW, partial + (size_t)blockIdx.x * ICP_NSUM);
 }
 
 __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ pose, int* __restrict__ frozen,
@@ -171,22 +89,9 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict_
         const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
         nw = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
         nv = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-        // Rodrigues: E = I + a K + c K^2, a = sin(th)/th, c = (1 - cos th)/th^2 = (sin(th/2)/(th/2))^2 / 2 (no cancellation at small th)
-        double a = 1.0, c = 0.5;
-        if (nw > 0.0) { a = sin(nw) / nw; const double h = sin(0.5 * nw) / (0.5 * nw); c = 0.5 * h * h; }
-        const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
         double E[3][3];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
-                E[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + c * k2;
-            }
-        double Pn[12];
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) Pn[3 * i + j] = (E[i][0] * pose[j] + E[i][1] * pose[3 + j]) + E[i][2] * pose[6 + j];
-            Pn[9 + i] = ((E[i][0] * pose[9] + E[i][1] * pose[10]) + E[i][2] * pose[11]) + xi[3 + i];
-        }
-        for (int i = 0; i < 12; ++i) pose[i] = Pn[i];
+        icp_exp_so3(w0, w1, w2, nw, E);
+        icp_apply_update(E, xi[3], xi[4], xi[5], pose);
         if (nw < tol_rot && nv < tol_trans) status = 1;
     }
     row[0] = count; row[1] = S[27]; row[2] = S[28]; row[3] = nw; row[4] = nv; row[5] = ratio; row[6] = (double)status;

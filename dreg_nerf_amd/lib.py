@@ -271,6 +271,9 @@ SIGNATURES = {
     # icp.hip
     "dreg_icp_workspace_bytes": (Z, [I, I]),
     "dreg_icp_refine": (I, [P, I, P, P, P, P, I, P, F, I, I, I, P, F, I] + [ctypes.c_double] * 3 + [P, P, P, P, P, Z, P]),
+    # icp_scene.hip: n_blocks, a HOST array of IcpBlock, a HOST pair mask, poses, max_dist, iters, the three tolerances, stats, pair_sums, rel, workspace, stream
+    "dreg_icp_scene_workspace_bytes": (Z, [I, P, P]),
+    "dreg_icp_scene_refine": (I, [I, P, P, P, F, I] + [ctypes.c_double] * 3 + [P, P, P, P, Z, P]),
     # pose_ransac.hip
     "dreg_pose_ransac_workspace_bytes": (Z, [I, I]),
     "dreg_pose_ransac": (I, [P, P, I, P, I, F, F, P, Z, P, P, P, P, P, P, P]),
@@ -360,6 +363,12 @@ class FieldBlock(ctypes.Structure):
 class RadianceBlock(ctypes.Structure):
     """dreg_radiance_block of include/dreg_nerf.h (one block's arguments of dreg_scene_voxel_grid)."""
     _fields_ = [("field", FieldBlock)] + [(n, P) for n in ("cw1", "cw2", "cw3", "dirbias")]
+
+
+class IcpBlock(ctypes.Structure):
+    """dreg_icp_block of include/dreg_nerf.h (one block's arguments of dreg_icp_scene_refine)."""
+    _fields_ = [("src", P), ("n", c_int), ("tgt_points", P), ("tgt_normals", P), ("cell_start", P), ("grid_lo", c_float * 3), ("cell", c_float),
+                ("nx", c_int), ("ny", c_int), ("nz", c_int)]
 
 
 def load_probe():

@@ -10,7 +10,8 @@ scene under the ground-truth and the synchronised poses; with --
 pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_mesh.json; with --scene_voxel_grid all its blocks
 extracted as ONE voxel grid in a block's own format under both pose sets, scene_voxel_grid_{gt,aligned}.pt / scene_voxel_mask_{gt,aligned}.pt /
 scene_voxel_grid.json; with --merge_scene all its blocks distilled into ONE NeRF block under both pose sets,
-merged_block_{gt,aligned}/model.pth / merged_block.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+merged_block_{gt,aligned}/model.pth / merged_block.json; with --refine_scene every scene's synchronised poses refined jointly by
+point-to-plane ICP over all block pairs at once, scene_refined_metrics_<split>.json, the scene products then taking the refined poses): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -94,17 +95,36 @@ def write_ransac(d, split, rows, ransac_rows, ransac_refined_rows=None, log=prin
     return out
 
 
-def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer=None, metrics=None, log=print):
-    """--register_scene [--scene_robust] [--render_scene] [--scene_mesh_field] [--scene_voxel_grid]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
+def register_scenes(cfg, ds, model, dev, rank=0, world=1, pair_fn=None, renderer=None, metrics=None, log=print, refiner=None, refined_rows=None):
+    """--register_scene [--scene_robust] [--refine_scene] [--render_scene] [--scene_mesh_field] [--scene_voxel_grid]: this rank's scenes registered as WHOLE scenes (dreg_nerf_amd/scene_reg.py):
     {scene: row of scene_metrics_{split}.json}.  Runs after the normal pass; get_scene, the forward calls and the synchronisation draw from no
-    random stream.  pair_fn / renderer / metrics are scene_reg's injection points (tests)."""
+    random stream.  pair_fn / renderer / metrics are scene_reg's injection points (tests).  With --refine_scene every scene's synchronised poses
+    are refined jointly (dreg_nerf_amd/scene_icp.py): its row of scene_refined_metrics_{split}.json goes into refined_rows, the scene
+    products below take the refined poses, and the returned rows are those of the unflagged run.  refiner(scene, G_sync) -> (G [K,4,4], info)
+    replaces scene_icp.refine_registered_scene (tests)."""
     from dreg_nerf_amd import scene_reg
     rows = {}
+    refine = getattr(cfg, "refine_scene", False)
     for i in ES.my_scenes(len(ds), rank, world):
         scene = ds.get_scene(i)
         name = str(scene[0].get("scene", i))
         res = scene_reg.register_scene(model, scene, robust=cfg.scene_robust, pair_fn=pair_fn, eval_batch=max(cfg.eval_batch, 1), device=dev)
         rows[name] = scene_reg.scene_row(res, scene)
+        if refine:   # the fine half at scene level: all pairs' point-to-plane residuals over the K - 1 free poses at once, from the synchronised poses
+            from dreg_nerf_amd import scene_icp
+            if refiner is not None:
+                G_ref, info = refiner(scene, res["G"])
+            else:
+                G_ref, info = scene_icp.refine_registered_scene(scene, res["G"], dev, cfg.icp_max_dist, cfg.icp_iters, cfg.icp_normals, log=lambda m: log(m, flush=True))
+            row = scene_icp.refined_scene_row(res, G_ref, info, scene)
+            if refined_rows is not None:
+                refined_rows[name] = row
+            kept = info["status"] in (2, 3)
+            log(f"{name}: joint ICP of {len(scene)} blocks, status {info['status']} after {info['iterations']} iterations, fitness {info['fitness']:.3f}: R_mean "
+                f"{row['R_mean_sync']:.3f} -> {row['R_mean']:.3f} deg, t_mean {row['t_mean_sync']:.4f} -> {row['t_mean']:.4f}; the scene products take the "
+                f"{'synchronised poses (the refinement ended with status 2 or 3)' if kept else 'refined poses'}", flush=True)
+            if not kept:
+                res = {**res, "G": torch.as_tensor(G_ref).double().cpu()}
         if cfg.render_scene:
             paths = [b.get("nerf_path", "") for b in scene]
             if renderer is not None or all(p and os.path.exists(p) for p in paths):
@@ -156,6 +176,16 @@ def write_scenes(d, split, scene_rows, log=print):
     return out
 
 
+def write_scenes_refined(d, split, refined_rows, log=print):
+    """scene_refined_metrics_{split}.json and RRE / RTE of the synchronised poses beside the jointly refined ones."""
+    from dreg_nerf_amd import scene_icp
+    out = scene_icp.write_scene_refined_metrics(os.path.join(d, f"scene_refined_metrics_{split}.json"), refined_rows)
+    kept = sum(1 for r in refined_rows.values() if r["status"] in (2, 3))
+    log(f"joint scene ICP, {len(refined_rows)} scenes ({kept} kept the synchronised poses): R_mean {out['R_mean_sync']:.3f} -> {out['R_mean']:.3f} deg, "
+        f"t_mean {out['t_mean_sync']:.4f} -> {out['t_mean']:.4f} -> {d}/scene_refined_metrics_{split}.json", flush=True)
+    return out
+
+
 def init_distributed(local_rank: int):
     """One process per GPU under torch.distributed.run: RCCL ('nccl' on ROCm).  DREG_EVAL_BACKEND=gloo with DREG_EVAL_ONE_GPU=1 is the test hook bench.py
     has too — several ranks on the one GPU of a test box exercise the sharding and the gather (tests/test_hip_eval_pipeline.py); never a measurement."""
@@ -172,8 +202,9 @@ def init_distributed(local_rank: int):
 
 def implied_flags(cfg):
     """The flags other flags imply: the scene render, the scene mesh and the scene voxel grid need the synchronised poses, so --render_scene,
-    --scene_mesh_field, --scene_voxel_grid and --merge_scene each imply --register_scene (and its scene_metrics file)."""
-    if cfg.render_scene or cfg.scene_mesh_field or getattr(cfg, "scene_voxel_grid", False) or getattr(cfg, "merge_scene", False):
+    --scene_mesh_field, --scene_voxel_grid, --merge_scene and --refine_scene each imply --register_scene (and its scene_metrics file)."""
+    if (cfg.render_scene or cfg.scene_mesh_field or getattr(cfg, "scene_voxel_grid", False) or getattr(cfg, "merge_scene", False) or
+            getattr(cfg, "refine_scene", False)):
         cfg.register_scene = True
     return cfg
 
@@ -297,14 +328,16 @@ def main():
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])
                 fgr_rows[data["scene"]] = {"R_mean": float(e["R_error_mean"]), "t_mean": float(e["t_error_mean"]),
                                            "R_med": float(e["R_error_med"]), "t_med": float(e["t_error_med"]), "time": sec}
-    scene_rows = {}
+    scene_rows, scene_refined_rows = {}, {}
     if cfg.register_scene:   # whole scenes, after the normal pass and apart from it: nothing above reads what this computes
         sds = SyntheticRegDataset(cfg.synthetic, cfg.synthetic_res, split, n_blocks=cfg.synthetic_blocks) if cfg.synthetic > 0 else ds
         with torch.no_grad():
-            scene_rows = register_scenes(cfg, sds, model, dev, rank, world)
+            scene_rows = register_scenes(cfg, sds, model, dev, rank, world, refined_rows=scene_refined_rows)
     rows, fgr_rows, refined_rows = ES.gather_rows(rows, world), ES.gather_rows(fgr_rows, world), ES.gather_rows(refined_rows, world)
     if cfg.register_scene:
         scene_rows = ES.gather_rows(scene_rows, world)
+        if getattr(cfg, "refine_scene", False):
+            scene_refined_rows = ES.gather_rows(scene_refined_rows, world)
     if cfg.ransac_pose:
         ransac_rows, ransac_refined_rows = ES.gather_rows(ransac_rows, world), ES.gather_rows(ransac_refined_rows, world)
     if rank == 0:
@@ -325,6 +358,8 @@ def main():
             write_ransac(d, split, rows, ransac_rows, ransac_refined_rows)
         if scene_rows:
             write_scenes(d, split, scene_rows)
+        if scene_refined_rows:
+            write_scenes_refined(d, split, scene_refined_rows)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -902,6 +902,39 @@ int dreg_icp_refine(const float* src, int Ns, const float* tgt_points, const flo
                     double tol_rot, double tol_trans, double eps_cond, double* stats, double* sums, int* corr, float* dist2,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- joint point-to-plane ICP of a whole scene
+ * (csrc/icp_scene.hip, csrc/icp_scan.h; rule: DESIGN.md §3n) dreg_icp_refine's residuals of ALL enabled ordered pairs (i -> j) of
+ * 2 <= n_blocks <= DREG_SCENE_MAX_BLOCKS blocks, minimised over the n_blocks - 1 free poses at once.  dreg_icp_block holds ONE block: src fp32
+ * [n,3], its points in the caller's order (device), and the same cloud as a target, sorted by the cells of a uniform grid as for dreg_icp_refine
+ * (tgt_points / tgt_normals fp32 [n,3], cell_start int32 [nx*ny*nz + 1], all device; grid_lo, cell, nx, ny, nz by value; cell >= max_dist;
+ * nx*ny*nz <= 2^24).  `blocks` is a HOST array of n_blocks of them, read before the call returns.  pair_mask: uint8 [n_blocks, n_blocks] in HOST
+ * memory or null (= all ones); the diagonal is ignored; a pair with a zero entry launches no work and contributes zeros.
+ * poses fp64 [n_blocks,12] on the device (R row-major, then t; block b -> block 0's frame), refined in place; block 0 is the anchor and its 12
+ * numbers are never written.  One launch forms the relative poses rel[i][j] = poses[j]^-1 poses[i] (fp64 [n_blocks,n_blocks,12]), then `iters`
+ * times: the correspondence kernel over all enabled pairs (per pair the 30 sums of dreg_icp_refine on (block i's src, block j's target,
+ * rel[i][j]), bit for bit) and the solve (assembly through the adjoints Ad(poses[j]^-1), Cholesky of the 6 (n_blocks - 1) unknowns, update, next
+ * rel): 1 + 2*iters launches on `stream`, no host synchronisation, no atomics.  stats fp64 [iters,7] per iteration: count, sum e^2 and sum d^2
+ * (totals over the pairs), the largest |omega_b| and |v_b|, the smallest pivot ratio, status (0 running, 1 converged: every |omega_b| < tol_rot and
+ * |v_b| < tol_trans, 2 fewer than 6 (n_blocks - 1) correspondences, 3 a pivot ratio <= eps_cond or a non-positive diagonal).  Status 2 / 3 leave
+ * all poses untouched; after any non-zero status the remaining rows repeat that row.  Optional device outputs (null = not written), as read or
+ * used by the last iteration that ran: pair_sums fp64 [n_blocks,n_blocks,30] (only enabled pairs are written), rel_out fp64
+ * [n_blocks,n_blocks,12].  workspace: dreg_icp_scene_workspace_bytes(n_blocks, blocks, pair_mask) bytes of device memory, 8-byte aligned (0: invalid
+ * arguments).  DREG_EINVAL before any launch: the guards of dreg_icp_refine per block, n_blocks out of range, a block with n < 1. */
+typedef struct dreg_icp_block {
+    const float* src;
+    int n;
+    const float* tgt_points;
+    const float* tgt_normals;
+    const int* cell_start;
+    float grid_lo[3];
+    float cell;
+    int nx, ny, nz;
+} dreg_icp_block;
+size_t dreg_icp_scene_workspace_bytes(int n_blocks, const dreg_icp_block* blocks, const uint8_t* pair_mask);
+int dreg_icp_scene_refine(int n_blocks, const dreg_icp_block* blocks, const uint8_t* pair_mask, double* poses, float max_dist, int iters,
+                          double tol_rot, double tol_trans, double eps_cond, double* stats, double* pair_sums, double* rel_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- robust pose from correspondences (RANSAC)
  * (csrc/pose_ransac.hip; rule and fp32 operation order: DESIGN.md §3g) for ONE pair per call.  a, b fp32 [N,3]: points of the source frame and
  * their matches in the target frame; triplets int32 [H,3]: the minimal sample of each hypothesis.  A hypothesis is invalid when two of its
