@@ -43,6 +43,12 @@ def config_parser(argv=None):
     p.add_argument("--pairs_per_step", type=int, default=1, help="pairs per optimizer step and GPU (reference: 1)")
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic shell-R scenes instead of a dataset on disk")
     p.add_argument("--synthetic_res", type=int, default=128)
+    p.add_argument("--backward", type=str, default="rays", choices=["rays", "samples"],
+                   help="train_ngp_nerf.py: the training backward: the ray kernel (dreg_ngp_render_bwd) or the sample list (dreg_ngp_render_train_samples, "
+                        "dreg_ngp_samples_grad, dreg_ngp_points_bwd; DESIGN.md 3o), which also carries opacity and depth gradients")
+    p.add_argument("--opacity_loss_weight", type=float, default=0.0,
+                   help="train_ngp_nerf.py --backward samples: weight of mean((opacity - alpha)^2) over all rays of the batch, alpha the images' own "
+                        "alpha channel (0 = off; the weight is not tuned)")
     p.add_argument("--dump_outputs", action="store_true",
                    help="eval: per scene, transformation_est.json and the registration's point clouds as PLY files (eval_nerf_regtr.py:313-438)")
     p.add_argument("--render_views", action="store_true",

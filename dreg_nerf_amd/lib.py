@@ -263,6 +263,11 @@ SIGNATURES = {
     # field_train.hip: x, dirs, n, base16, color16, the level table, model_aabb, g_sigma, g_rgb, grad_base, grad_color, workspace, bytes, stream
     "dreg_ngp_points_bwd_workspace_bytes": (Z, [ctypes.c_long]),
     "dreg_ngp_points_bwd": (I, [P, P, ctypes.c_long, P, P] + [P] * 5 + [P, P, P, P, P, P, Z, P]),
+    # render_samples.hip: dreg_ngp_render_train's arguments up to queue, then capacity, the nine record arrays, slots, stream;
+    # n, seven record arrays, viewdirs, rgb, opacity, depth, the three upstream gradients, dt, dirs, g_sigma, g_c, stream
+    "dreg_ngp_render_train_samples": (I, [P, P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 5
+                                      + [ctypes.c_long] + [P] * 9 + [P, P]),
+    "dreg_ngp_samples_grad": (I, [ctypes.c_long] + [P] * 7 + [P] * 4 + [P] * 3 + [F] + [P] * 4),
     # image_metrics.hip
     "dreg_image_metrics_workspace_bytes": (Z, [I, I, I, I]),
     "dreg_image_metrics": (I, [P, P, I, I, I, I, P] + [P] * 6 + [P, Z, P]),
@@ -331,6 +336,7 @@ PROBE_SIGNATURES = {
     "dreg_render_bwd_set_waves": (None, [I]),
     "dreg_render_scene_set_waves": (None, [I]),
     "dreg_points_bwd_set_waves": (None, [I]),
+    "dreg_render_samples_set_waves": (None, [I]),
     "dreg_scene_grid_set_waves": (None, [I]),
     "dreg_scene_grid_set_lanes_z": (None, [I]),
 }

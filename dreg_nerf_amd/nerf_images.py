@@ -68,7 +68,8 @@ def load_renderings(dataset: str, root_dir: str, scene: str, split: str, multi_b
 
 class SubjectImages:
     """One scene (or one block of it) on the device: images uint8 [N,H,W,4], camtoworlds fp32 [N,4,4], K fp32 [3,3].
-    sample(num_rays) draws random (image, x, y) pixels over all images and returns (Rays [num_rays,3], pixels fp32 [num_rays,3] over white)."""
+    sample(num_rays) draws random (image, x, y) pixels over all images and returns (Rays [num_rays,3], pixels fp32 [num_rays,3] over white),
+    and with with_alpha=True the pixels' alpha [num_rays] as a third value."""
 
     def __init__(self, images: np.ndarray, camtoworlds: np.ndarray, focal: float, device, block_id: Optional[int] = None):
         self.device = torch.device(device)
@@ -90,8 +91,9 @@ class SubjectImages:
             return [SubjectImages(i, c, focal, device, block_id=b) for b, (i, c) in enumerate(zip(images, c2w))]
         return [SubjectImages(images, c2w, focal, device)]
 
-    def rays_of(self, img: torch.Tensor, x: torch.Tensor, y: torch.Tensor):
-        """Rays through pixel centres (x, y) of images img (render.pixel_rays' rule, OpenGL cameras) and their pixels over white."""
+    def rays_of(self, img: torch.Tensor, x: torch.Tensor, y: torch.Tensor, with_alpha: bool = False):
+        """Rays through pixel centres (x, y) of images img (render.pixel_rays' rule, OpenGL cameras) and their pixels over white; with_alpha:
+        also the pixels' alpha channel in [0,1], fp32 [N], as a third value (the target of NGPTrainer's opacity loss)."""
         K = self.K
         c2w = self.camtoworlds[img]
         cam = torch.stack([(x.float() - K[0, 2] + 0.5) / K[0, 0], -(y.float() - K[1, 2] + 0.5) / K[1, 1], -torch.ones_like(x, dtype=torch.float32)], dim=-1)
@@ -100,14 +102,16 @@ class SubjectImages:
         viewdirs = directions / torch.linalg.norm(directions, dim=-1, keepdim=True)
         rgba = self.images[img, y, x].float() / 255.0
         pixels = rgba[:, :3] * rgba[:, 3:4] + (1.0 - rgba[:, 3:4])
+        if with_alpha:
+            return Rays(origins, viewdirs.contiguous()), pixels, rgba[:, 3].contiguous()
         return Rays(origins, viewdirs.contiguous()), pixels
 
-    def sample(self, num_rays: int, generator: Optional[torch.Generator] = None):
+    def sample(self, num_rays: int, generator: Optional[torch.Generator] = None, with_alpha: bool = False):
         n = len(self)
         img = torch.randint(0, n, (num_rays,), device=self.device, generator=generator)
         x = torch.randint(0, self.WIDTH, (num_rays,), device=self.device, generator=generator)
         y = torch.randint(0, self.HEIGHT, (num_rays,), device=self.device, generator=generator)
-        return self.rays_of(img, x, y)
+        return self.rays_of(img, x, y, with_alpha) if with_alpha else self.rays_of(img, x, y)
 
     def view(self, i: int):
         """(Rays [H,W,3], pixels [H,W,3] over white) of image i, for validation."""

@@ -862,6 +862,33 @@ int dreg_ngp_points_bwd(const float* x, const float* dirs, long n, const void* b
                         const float* model_aabb, const float* g_sigma, const float* g_rgb, float* grad_base, float* grad_color,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- training of a NeRF block on a sample list
+ * (csrc/render_samples.hip; rule: DESIGN.md §3o).
+ * dreg_ngp_render_train_samples = dreg_ngp_render_train (same arguments, same rgb / opacity / depth / n_samples bit for bit) that also writes
+ * one record per surviving sample into caller-owned device arrays of `capacity` records: s_ray / s_ord int32 (the ray; the number of earlier
+ * survivors of it), s_t fp32 (t_mid), s_x fp32 [.,3] (the sample position), s_T_next fp32 (the survivors' transmittance after the sample), s_w
+ * fp32 (the weight), s_c fp32 [.,3] (the colour), s_P fp32 [.,3] and s_Pd fp32 (sum w c and sum w t up to and including the sample).  slots: one
+ * u64 zeroed by the caller on `stream`; on completion the TRUE number of survivors, whatever the capacity.  A record whose slot is >= capacity
+ * is not written; the per-ray outputs do not depend on the capacity.  The order of the list depends on the scheduling: sort by (ray, ord).
+ * DREG_EINVAL with nothing launched for n_rays < 0, capacity < 0, a null record array with capacity > 0, and whatever dreg_ngp_render_train
+ * rejects; n_rays == 0 returns DREG_OK first.
+ * dreg_ngp_samples_grad: n records (any order) and the per-ray upstream gradients g_rgb fp32 [n_rays,3], g_opacity, g_depth fp32 [n_rays] (each
+ * may be null = zeros; all three null: DREG_OK, nothing launched or written) -> dirs fp32 [n,3] = viewdirs[ray], g_sigma fp32 [n], g_c fp32 [n,3]:
+ *   g_c = w g_rgb,   g_sigma = dt (sum_ch g_rgb (T_next c - (rgb - P)) + g_opacity (1 - opacity) + g_depth (T_next t - (depth - Pd)))
+ * with rgb / opacity / depth the forward's per-ray outputs.  With s_x these are dreg_ngp_points_bwd's x, dirs, g_sigma, g_rgb. */
+int dreg_ngp_render_train_samples(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
+                                  const uint32_t* coarse_bits, const void* table, const void* w1, const void* w2, const void* cw1, const void* cw2, const void* cw3,
+                                  const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                                  const float* roi_aabb, const float* scene_aabb, const float* model_aabb, float near_plane, float far_plane,
+                                  float render_step_size, float alpha_thre, float early_stop_eps, const float* bkgd,
+                                  float* rgb, float* opacity, float* depth, unsigned long long* n_samples, void* queue,
+                                  long capacity, int* s_ray, int* s_ord, float* s_t, float* s_x, float* s_T_next, float* s_w, float* s_c, float* s_P, float* s_Pd,
+                                  void* slots, void* stream);
+int dreg_ngp_samples_grad(long n, const int* s_ray, const float* s_t, const float* s_T_next, const float* s_w, const float* s_c, const float* s_P,
+                          const float* s_Pd, const float* viewdirs, const float* rgb, const float* opacity, const float* depth,
+                          const float* g_rgb, const float* g_opacity, const float* g_depth, float render_step_size,
+                          float* dirs, float* g_sigma, float* g_c, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- image metrics of rendered views
  * (csrc/image_metrics.hip; rule: DESIGN.md §3d) SSIM, MSE and PSNR of the reference's evaluate() (eval_ngp_nerf.py:24-31,214-229,
  * conerf/loss/ssim_torch.py) for N image pairs in one call.  pred, gt: fp32 [N,H,W,C], channel-last, contiguous, device; 1 <= C <= 4,

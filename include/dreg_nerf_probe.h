@@ -52,7 +52,8 @@ void dreg_render_pair_set_waves(int n);              /* one-wave workgroups of d
 void dreg_render_scene_set_waves(int n);             /* one-wave workgroups of dreg_ngp_render_scene's persistent launch (default 2048); same results at every width */
 void dreg_render_bwd_set_waves(int n);               /* one-wave workgroups of dreg_ngp_render_bwd's persistent launch (default 2048); same gradients at every width */
 void dreg_points_bwd_set_waves(int n);               /* one-wave workgroups of dreg_ngp_points_bwd's persistent launch (default 2048); same MLP gradients at every width */
-void dreg_conv_set_narrow_small(int on);              /* 1 (default): launches of < 224 128 x 128 tiles use 128 x 64 tiles (twice the workgroups) */
+void dreg_render_samples_set_waves(int n);           /* one-wave workgroups of dreg_ngp_render_train_samples' persistent launch (default 2048); same per-ray results and sorted list at every width */
+void dreg_conv_set_narrow_small(int on);             /* 1 (default): launches of < 224 128 x 128 tiles use 128 x 64 tiles (twice the workgroups) */
 void dreg_scene_grid_set_waves(int n);               /* one-wave workgroups of dreg_scene_voxel_grid's launch at most (default 16384); same bytes at every width */
 void dreg_scene_grid_set_lanes_z(int on);            /* 1 (default): a wave's lanes of dreg_scene_voxel_grid run along z (the output's fastest axis); 0: along x (the hash tables'); same bytes */
 

@@ -3,7 +3,10 @@ occupancy grid, tcnn's initial field.  Reports ms per step split into occupancy 
 backward (loss + dreg_ngp_render_bwd), fused Adam and host, with surviving samples/s and the hash-table scatter's added bytes per second of the
 backward launch (an upper-bound time: the launch also re-marches and runs both networks).
 
-    python tools/bench_train_ngp.py --steps 50 --warmup 20 [--out profiles/train_ngp_bench.json]
+    python tools/bench_train_ngp.py --steps 50 --warmup 20 [--backward samples] [--out profiles/train_ngp_bench.json]
+
+--backward samples times the sample-list path (dreg_ngp_render_train_samples, the sort, dreg_ngp_samples_grad, dreg_ngp_points_bwd)
+instead of the ray backward; the figures keep their names (forward_ms then includes the list write and the sort).
 """
 import argparse
 import json
@@ -52,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--backward", choices=["rays", "samples"], default="rays")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -74,7 +78,10 @@ def main():
         e = [ev() for _ in range(4)]
         e[0].record()
         rs, px = tr.data.sample(tr.num_rays)
-        rgb, opac, _, n = ngp_train.render_image_train(field, grid, rs, aabb, tr.render_step_size, tr.bkgd)
+        if args.backward == "samples":
+            rgb, opac, _, n = ngp_train.render_image_train(field, grid, rs, aabb, tr.render_step_size, tr.bkgd, backward="samples")
+        else:
+            rgb, opac, _, n = ngp_train.render_image_train(field, grid, rs, aabb, tr.render_step_size, tr.bkgd)
         e[1].record()
         alive = opac.squeeze(-1) > 0
         loss = torch.nn.functional.smooth_l1_loss(rgb[alive], px[alive])
@@ -112,7 +119,7 @@ def main():
            "host_ms": round(step - fwd - bwd - adam, 3), "surviving_samples_per_step": samples // S, "rays_per_step": rays // S,
            "surviving_samples_per_s_fwd": round(samples / S / (fwd * 1e-3)), "surviving_samples_per_s_bwd": round(samples / S / (bwd * 1e-3)),
            "hash_scatter_TBps_over_backward": round(samples / S * 1024 / (bwd * 1e-3) / 1e12, 4), "steps": S, "warmup": args.warmup,
-           "views": "800x800", "grid": 128, "target_samples": ngp_train.TARGET_SAMPLES}
+           "views": "800x800", "grid": 128, "target_samples": ngp_train.TARGET_SAMPLES, "backward": args.backward}
     print(json.dumps(res), flush=True)
     if args.out:
         with open(args.out, "w") as fp:

@@ -61,7 +61,8 @@ def train_block(config, train_set: SubjectImages, val_set: SubjectImages, out_di
     aabb = [float(v) for v in config.aabb]
     field = ngp.NGPradianceField(aabb=aabb).to(device)
     grid = ngp.OccupancyGrid(roi_aabb=aabb, resolution=128, contraction_type=ngp.ContractionType.AABB).to(device)
-    trainer = ngp_train.NGPTrainer(field, grid, train_set, aabb, config.max_iterations)
+    trainer = ngp_train.NGPTrainer(field, grid, train_set, aabb, config.max_iterations, backward=config.backward,
+                                   opacity_loss_weight=config.opacity_loss_weight)
     os.makedirs(out_dir, exist_ok=True)
     ckpt = CheckPointManager(save_path=out_dir, max_to_keep=100, keep_checkpoint_every_n_hours=0.5)
     meta = {"aabb": aabb, "unbounded": False, "grid_resolution": 128, "contraction_type": ngp.ContractionType.AABB, "near_plane": None,
