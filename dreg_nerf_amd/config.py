@@ -127,6 +127,14 @@ def config_parser(argv=None):
                    help="eval_nerf_regtr.py: implies --register_scene; then every scene's synchronised poses are refined JOINTLY by point-to-plane ICP over all "
                         "ordered block pairs at once (fused K-block kernels, DESIGN.md 3n; --icp_max_dist, --icp_iters, --icp_normals apply): "
                         "scene_refined_metrics_{split}.json, and the scene products of the same run take the refined poses")
+    p.add_argument("--photo_refine", action="store_true",
+                   help="eval_nerf_regtr.py: after the normal pass, refine every scene's pose photometrically (analysis by synthesis through the field's input "
+                        "gradients, DESIGN.md 3p) from the ICP-refined pose when --refine_pose is also given, else from the predicted pose, per scene whose "
+                        "block checkpoints are on disk: photo_refined_metrics_{split}.json next to metrics_{split}.json, which is unchanged")
+    p.add_argument("--photo_iters", type=int, default=200, help="--photo_refine: Adam iterations (not tuned)")
+    p.add_argument("--photo_rays", type=int, default=4096, help="--photo_refine: rays per iteration and direction (not tuned)")
+    p.add_argument("--photo_lr", type=float, default=2e-3, help="--photo_refine: Adam's learning rate on the twist (not tuned)")
+    p.add_argument("--photo_depth_weight", type=float, default=0.1, help="--photo_refine: weight of the depth term of the loss (not tuned)")
     p.add_argument("--eval_batch", type=int, default=4, help="eval: pairs per forward call (reference: 1; results per scene do not depend on it beyond bf16 rounding)")
     p.add_argument("--extract_grids", action="store_true",
                    help="eval_nerf_regtr.py: extract the voxel grids of the split's NeRF blocks first (what eval_ngp_nerf.py does, same files) and register from the device-resident grids, pipelined")

@@ -1,7 +1,8 @@
 """Training of a NeRF block's field on POINTS: field_points(field, x, dirs) -> (sigma [N], rgb [N,3]), differentiable with
 respect to field.mlp_base.params and field.color_mlp.params.  The forward is the inference forward (dreg_ngp_density_fwd_ws + dreg_ngp_rgb_dir_fwd
 on the field's fp16 copies: the bits of query_raw / query_rgb), the backward one dreg_ngp_points_bwd (csrc/field_train.hip).  Positions and
-directions get no gradient.  ngp_train.NGPAdam steps the field and refreshes its fp16 copies as for the ray training."""
+directions receive gradients when they require them: one dreg_ngp_points_input_grad (csrc/field_input_grad.hip); when neither
+does, nothing more is launched.  ngp_train.NGPAdam steps the field and refreshes its fp16 copies as for the ray training."""
 import torch
 
 from . import lib as L
@@ -27,6 +28,24 @@ def points_bwd(field, x, dirs, g_sigma, g_rgb, grad_base=None, grad_color=None):
     return grad_base, grad_color
 
 
+def points_input_grad(field, x, dirs, g_sigma, g_rgb, want_x=True, want_dir=True):
+    """One dreg_ngp_points_input_grad launch: (dL/dx [N,3] or None, dL/ddir [N,3] or None) of (g_sigma . sigma + g_rgb . rgb) with the parameters
+    frozen; written, not added.  x, dirs fp32 [N,3] contiguous on the field's device; g_sigma [N] / g_rgb [N,3] or None (zeros: the outputs
+    are zeros).  dirs is differentiated as given (not renormalised)."""
+    if getattr(field, "unbounded", False):
+        raise NotImplementedError("points_input_grad: the contracted (unbounded) field is not implemented")
+    base16, col16 = field._prepared()
+    dev = base16.device
+    n = x.shape[0]
+    gx = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_x else None
+    gd = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_dir else None
+    if n and (want_x or want_dir):
+        L.check(L.load().dreg_ngp_points_input_grad(L.ptr(x), L.ptr(dirs), n, base16.data_ptr(), col16.data_ptr(), *field._levels,
+                                                    L.f6(field._aabb_host()), L.ptr(g_sigma), L.ptr(g_rgb), L.ptr(gx), L.ptr(gd), L.stream()),
+                "dreg_ngp_points_input_grad")
+    return gx, gd
+
+
 class _FieldPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, base_params, color_params, field, x, dirs):
@@ -43,13 +62,19 @@ class _FieldPoints(torch.autograd.Function):
         x, dirs = ctx.saved_tensors
         gs = None if g_sigma is None else g_sigma.float().contiguous()
         gc = None if g_rgb is None else g_rgb.float().contiguous()
-        grad_base, grad_color = points_bwd(ctx.field, x, dirs, gs, gc)
-        return grad_base, grad_color, None, None, None
+        grad_base = grad_color = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            grad_base, grad_color = points_bwd(ctx.field, x, dirs, gs, gc)
+        gx = gd = None
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            gx, gd = points_input_grad(ctx.field, x, dirs, gs, gc, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+        return grad_base, grad_color, None, gx, gd
 
 
 def field_points(field, x: torch.Tensor, dirs: torch.Tensor):
-    """(sigma [N], rgb [N,3]) of the field at the points x [N,3] (its own frame) seen along the unit directions dirs [N,3]; the bits of
-    field.query_raw(x)[0] and field.query_rgb(dirs, field.query_raw(x)[1][:, 1:]).  Bounded fields only."""
+    """(sigma [N], rgb [N,3]) of the field at the points x [N,3] (its own frame) seen along the directions dirs [N,3] (unit for the field's
+    colours; differentiated as given); the bits of field.query_raw(x)[0] and field.query_rgb(dirs, field.query_raw(x)[1][:, 1:]).  x and dirs
+    receive gradients when they require them (the straight-through gradient).  Bounded fields only."""
     if getattr(field, "unbounded", False):
         raise NotImplementedError("field_points: the contracted (unbounded) field is not implemented")
     dev = field.mlp_base.params.device

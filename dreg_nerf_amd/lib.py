@@ -268,6 +268,10 @@ SIGNATURES = {
     "dreg_ngp_render_train_samples": (I, [P, P, P, ctypes.c_long, P, I, I, I, P] + [P] * 6 + [P] * 5 + [P, P, P] + [F] * 5 + [P] + [P] * 5
                                       + [ctypes.c_long] + [P] * 9 + [P, P]),
     "dreg_ngp_samples_grad": (I, [ctypes.c_long] + [P] * 7 + [P] * 4 + [P] * 3 + [F] + [P] * 4),
+    # field_input_grad.hip: x, dirs, n, base16, color16, the level table, model_aabb, g_sigma, g_rgb, grad_x, grad_dir, stream;
+    # n, s_ray, s_t, grad_x, grad_dir, n_rays, grad_o, grad_d, stream
+    "dreg_ngp_points_input_grad": (I, [P, P, ctypes.c_long, P, P] + [P] * 5 + [P, P, P, P, P, P]),
+    "dreg_ngp_samples_ray_grad": (I, [ctypes.c_long, P, P, P, P, ctypes.c_long, P, P, P]),
     # image_metrics.hip
     "dreg_image_metrics_workspace_bytes": (Z, [I, I, I, I]),
     "dreg_image_metrics": (I, [P, P, I, I, I, I, P] + [P] * 6 + [P, Z, P]),

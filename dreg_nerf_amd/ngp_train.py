@@ -3,7 +3,8 @@
   render_image_train   the renderer with stratified marching (csrc/render.hip dreg_ngp_render_train) as an autograd Function whose backward is
                        csrc/render_train.hip dreg_ngp_render_bwd: rgb is differentiable w.r.t. mlp_base.params and color_mlp.params;
                        with backward="samples"  the forward keeps its surviving samples as a list (csrc/render_samples.hip) and
-                       the backward is dreg_ngp_samples_grad + dreg_ngp_points_bwd: rgb, opacity and depth are all differentiable
+                       the backward is dreg_ngp_samples_grad + dreg_ngp_points_bwd: rgb, opacity and depth are all differentiable, also with
+                       respect to the rays' origins and viewdirs (dreg_ngp_points_input_grad + dreg_ngp_samples_ray_grad)
   NGPAdam              torch.optim.Adam(lr=1e-2, eps=1e-15) whose step is one fused pass per parameter (dreg_ngp_adam_step) that also refreshes the
                        field's fp16 inference copies and zeroes the gradient; state_dict layout = torch.optim.Adam's
   NGPTrainer           the per-step rule: occupancy update every 16 steps, random rays over the block's images, render, smooth-L1 on the alive
@@ -138,9 +139,27 @@ def samples_grad(rec, d, rgb, opacity, depth, g_rgb, g_opacity, g_depth, dt):
     return dirs, g_sigma, g_c
 
 
+def samples_ray_grad(field, rec, grads, with_rgb, n_rays):
+    """(dL/dorigins [n_rays,3], dL/dviewdirs [n_rays,3]) from samples_grad's output `grads` (None: zeros) on the canonical-order list `rec`:
+    dreg_ngp_points_input_grad at rec["x"], then dreg_ngp_samples_ray_grad.  The t_k, the survivor set and the jitter are constants."""
+    from . import field_train
+    dev = rec["ray"].device
+    n = rec["ray"].shape[0]
+    grad_o = torch.empty(n_rays, 3, dtype=torch.float32, device=dev)
+    grad_d = torch.empty(n_rays, 3, dtype=torch.float32, device=dev)
+    if grads is None or n == 0:
+        return grad_o.zero_(), grad_d.zero_()
+    dirs, g_sigma, g_c = grads
+    gx, gdir = field_train.points_input_grad(field, rec["x"], dirs, g_sigma, g_c if with_rgb else None)
+    L.check(L.load().dreg_ngp_samples_ray_grad(n, L.ptr(rec["ray"]), L.ptr(rec["t"]), L.ptr(gx), L.ptr(gdir), n_rays, L.ptr(grad_o), L.ptr(grad_d),
+                                               L.stream()), "dreg_ngp_samples_ray_grad")
+    return grad_o, grad_d
+
+
 class _RenderTrainSamples(torch.autograd.Function):
     """The training forward that keeps its survivors: rgb, opacity and depth are differentiable; the backward is
-    dreg_ngp_samples_grad on the sorted list, then dreg_ngp_points_bwd."""
+    dreg_ngp_samples_grad on the sorted list, then dreg_ngp_points_bwd (parameters that require grad) and dreg_ngp_points_input_grad +
+    dreg_ngp_samples_ray_grad (origins / viewdirs that require grad)."""
 
     @staticmethod
     def forward(ctx, base_params, color_params, field, occupancy_grid, o, d, jitter, scene_aabb, dt, bkgd, alpha_thre, capacity):
@@ -165,14 +184,20 @@ class _RenderTrainSamples(torch.autograd.Function):
         field = ctx.field
         base16, col16 = field._prepared()
         dev = base16.device
-        grad_base = torch.zeros(base16.numel(), dtype=torch.float32, device=dev)
-        grad_color = torch.zeros(col16.numel(), dtype=torch.float32, device=dev)
+        want_params = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_rays = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        grad_base = grad_color = grad_o = grad_d = None
+        if want_params:                         # (frozen parameters, field.requires_grad_(False): neither the buffers nor dreg_ngp_points_bwd)
+            grad_base = torch.zeros(base16.numel(), dtype=torch.float32, device=dev)
+            grad_color = torch.zeros(col16.numel(), dtype=torch.float32, device=dev)
         gs = [None if g is None else g.float().contiguous() for g in (g_rgb, g_op, g_dep)]
         out = samples_grad(ctx.rec, d, rgb, opacity, depth, gs[0], gs[1], gs[2], ctx.dt)
-        if out is not None:
+        if out is not None and want_params:
             dirs, g_sigma, g_c = out
             field_train.points_bwd(field, ctx.rec["x"], dirs, g_sigma, g_c if gs[0] is not None else None, grad_base, grad_color)
-        return grad_base, grad_color, None, None, None, None, None, None, None, None, None, None
+        if want_rays:                           # through the field into x_k = o + t_k d and dirs_k = d, then along the rays
+            grad_o, grad_d = samples_ray_grad(field, ctx.rec, out, gs[0] is not None, d.shape[0])
+        return grad_base, grad_color, None, None, grad_o, grad_d, None, None, None, None, None, None
 
 
 def render_image_train(field, occupancy_grid, rays, scene_aabb, render_step_size: float, render_bkgd=None, alpha_thre: float = 0.0,
@@ -181,9 +206,12 @@ def render_image_train(field, occupancy_grid, rays, scene_aabb, render_step_size
     depth [N,1], n_rendering_samples int).  jitter fp32 [N] in [0,1) (the per-ray offset u of t_min + u dt) is drawn with torch.rand when not
     given.  backward="rays": opacity and depth are detached.  backward="samples" (DESIGN.md §3o): the forward keeps its surviving samples
     (sample_capacity records at first, default min(N n_max, 2^20); launched once more at the true count when they do not fit) and all three
-    outputs are differentiable."""
+    outputs are differentiable, also with respect to rays.origins / rays.viewdirs when they require grad (the sample distances,
+    the survivor set and the jitter are constants); the ray backward carries no such gradient and raises."""
     if backward not in BACKWARDS:
         raise ValueError(f"render_image_train: backward must be one of {BACKWARDS}, not {backward!r}")
+    if backward != "samples" and torch.is_grad_enabled() and (getattr(rays.origins, "requires_grad", False) or getattr(rays.viewdirs, "requires_grad", False)):
+        raise ValueError('render_image_train: origins / viewdirs that require grad need backward="samples" (the ray backward carries no ray gradient)')
     if sample_capacity is not None and int(sample_capacity) < 0:
         raise ValueError("render_image_train: sample_capacity must be >= 0")
     if getattr(field, "unbounded", False) or scene_aabb is None:

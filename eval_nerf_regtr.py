@@ -11,7 +11,8 @@ pose sets, scene_field_mesh_gt.ply / scene_field_mesh_aligned.ply / scene_field_
 extracted as ONE voxel grid in a block's own format under both pose sets, scene_voxel_grid_{gt,aligned}.pt / scene_voxel_mask_{gt,aligned}.pt /
 scene_voxel_grid.json; with --merge_scene all its blocks distilled into ONE NeRF block under both pose sets,
 merged_block_{gt,aligned}/model.pth / merged_block.json; with --refine_scene every scene's synchronised poses refined jointly by
-point-to-plane ICP over all block pairs at once, scene_refined_metrics_<split>.json, the scene products then taking the refined poses): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
+point-to-plane ICP over all block pairs at once, scene_refined_metrics_<split>.json, the scene products then taking the refined poses, DESIGN.md §3n;
+with --photo_refine every scene's pose refined photometrically through the field's input gradients, photo_refined_metrics_<split>.json): per-scene RRE/RTE + forward time (with a device sync, unlike the reference — quirk Q13) written to
 <root>/eval/<expname>/<dataset>/metrics_<split>.json with the reference's schema.  Scenes are sharded over ranks
 when launched with torch.distributed.run (replicas only, results gathered on rank 0)."""
 import json
@@ -45,9 +46,9 @@ def _row(err, dt):
     return {"R_mean": float(err["R_error_mean"]), "t_mean": float(err["t_error_mean"]), "R_med": float(err["R_error_med"]), "t_med": float(err["t_error_med"]), "time": dt}
 
 
-def refine_scene_pose(cfg, data, pred, dev, refiner=None, log=print):
-    """--refine_pose for one scene: the row of refined_metrics_{split}.json.  Target normals from the target block's field when --icp_normals field
-    and its checkpoint is on disk, else by PCA (a printed line says so)."""
+def refine_scene_pose(cfg, data, pred, dev, refiner=None, log=print, with_pose=False):
+    """--refine_pose for one scene: the row of refined_metrics_{split}.json (with_pose: and the pose [1,3,4] it scores).  Target normals from the
+    target block's field when --icp_normals field and its checkpoint is on disk, else by PCA (a printed line says so)."""
     from dreg_nerf_amd import icp
     field = None
     tp = data.get("tgt_nerf_path", "")
@@ -56,9 +57,39 @@ def refine_scene_pose(cfg, data, pred, dev, refiner=None, log=print):
         field = load_block(tp, dev)[0]
         if field.unbounded:
             field = None
-    row, _ = icp.refine_scene(_points(data, "src"), _points(data, "tgt"), pred["pose"][-1], data["pose"], field, cfg.icp_max_dist, cfg.icp_iters,
-                              refiner=refiner, log=lambda m: log(m, flush=True), scene=str(data["scene"]))
-    return row
+    row, pose = icp.refine_scene(_points(data, "src"), _points(data, "tgt"), pred["pose"][-1], data["pose"], field, cfg.icp_max_dist, cfg.icp_iters,
+                                 refiner=refiner, log=lambda m: log(m, flush=True), scene=str(data["scene"]))
+    return (row, pose) if with_pose else row
+
+
+def photo_refine_scenes(cfg, jobs, dev, refine=None, log=print):
+    """--photo_refine: the photometric refinement of every scene of `jobs` = [(scene, source checkpoint, target checkpoint, start pose [3,4], gt pose)],
+    after the normal pass: {scene: row of photo_refined_metrics_{split}.json}.  A scene whose blocks are not on disk is skipped with a
+    printed line.  refine(src_path, tgt_path, start, gt) -> (row, pose) replaces photo_refine.photo_refine_scene (tests)."""
+    rows = {}
+    for scene, sp, tp, start, gt in jobs:
+        if not (sp and tp and os.path.exists(sp) and os.path.exists(tp)):
+            log(f"{scene}: no NeRF blocks on disk, pose not refined photometrically", flush=True)
+            continue
+        if refine is None:
+            from dreg_nerf_amd.photo_refine import photo_refine_scene
+            row, _ = photo_refine_scene(sp, tp, start, gt, cfg.dataset, dev, cfg.photo_iters, cfg.photo_rays, cfg.photo_lr, cfg.photo_depth_weight, cfg.seed)
+        else:
+            row, _ = refine(sp, tp, start, gt)
+        rows[scene] = row
+        log(f"{scene}: photometric refinement, {row['iterations']} iterations: R {row['R_start']:.3f} -> {row['R_mean']:.3f} deg, "
+            f"t {row['t_start']:.4f} -> {row['t_mean']:.4f}", flush=True)
+    return rows
+
+
+def write_photo_refined(d, split, photo_rows, log=print):
+    """photo_refined_metrics_{split}.json: icp.write_refined_metrics' schema (ES.summary's layout), every row with its start errors and iterations."""
+    from dreg_nerf_amd import icp
+    out = icp.write_refined_metrics(os.path.join(d, f"photo_refined_metrics_{split}.json"), photo_rows)
+    n = max(len(photo_rows), 1)
+    log(f"photometric refinement, {len(photo_rows)} scenes: R_mean {sum(r['R_start'] for r in photo_rows.values()) / n:.3f} -> {out['R_mean']:.3f} deg, "
+        f"t_mean {sum(r['t_start'] for r in photo_rows.values()) / n:.4f} -> {out['t_mean']:.4f} -> {d}/photo_refined_metrics_{split}.json", flush=True)
+    return out
 
 
 def write_refined(d, split, rows, refined_rows, log=print):
@@ -234,6 +265,7 @@ def main():
     if CheckPointManager(verbose=rank == 0).load_no_config(ckpt_path, models={"model": model}, map_location=dev) == 0 and not os.path.exists(ckpt_path):
         print(f"[WARNING] no checkpoint at {ckpt_path}: evaluating random-init weights", flush=True)
     rows, fgr_rows, refined_rows = {}, {}, {}
+    photo_jobs = []
     ransac_rows, ransac_refined_rows = {}, {}
     per_scene_extras = cfg.dump_outputs or cfg.fgr_baseline or cfg.render_views or cfg.render_merged or cfg.merged_mesh or cfg.merged_mesh_field
     mine = ES.my_scenes(len(ds), rank, world)
@@ -272,8 +304,12 @@ def main():
             model.check_inputs()      # a grid with values outside its voxel_mask (the row-list stem would have dropped them) is an error of THESE scenes
             for data, pred in zip(batch, preds):
                 rows[data["scene"]] = _row(LS.evaluate_camera_alignment(pred["pose"][-1], data["pose"]), dt)
+                start = pred["pose"][-1]
                 if cfg.refine_pose:    # the "fine" half: point-to-plane ICP from the predicted pose (refine_registration, global_registration.py:85-93);
-                    refined_rows[data["scene"]] = refine_scene_pose(cfg, data, pred, dev)      # the forward calls and their batches are the unflagged run's
+                    refined_rows[data["scene"]], start = refine_scene_pose(cfg, data, pred, dev, with_pose=True)      # the forward calls and their batches are the unflagged run's
+                if cfg.photo_refine:   # run after the pass (below), from the ICP-refined pose when there is one, else from the predicted pose
+                    photo_jobs.append((data["scene"], data.get("src_nerf_path", ""), data.get("tgt_nerf_path", ""),
+                                       start.detach().reshape(3, 4).double().cpu(), data["pose"].detach().reshape(-1, 4)[:3].double().cpu()))
                 if cfg.ransac_pose:    # the robust estimate from the same prediction's correspondences; nothing above reads it
                     ransac_rows[data["scene"]], rp = ransac_scene_pose(cfg, data, pred)
                     if cfg.refine_pose:
@@ -328,6 +364,9 @@ def main():
                 e = LS.evaluate_camera_alignment(T[None].float(), data["pose"])
                 fgr_rows[data["scene"]] = {"R_mean": float(e["R_error_mean"]), "t_mean": float(e["t_error_mean"]),
                                            "R_med": float(e["R_error_med"]), "t_med": float(e["t_error_med"]), "time": sec}
+    photo_rows = {}
+    if cfg.photo_refine:     # per scene, after the normal pass and apart from it (it needs autograd; the pass above runs under no_grad)
+        photo_rows = ES.gather_rows(photo_refine_scenes(cfg, photo_jobs, dev), world)
     scene_rows, scene_refined_rows = {}, {}
     if cfg.register_scene:   # whole scenes, after the normal pass and apart from it: nothing above reads what this computes
         sds = SyntheticRegDataset(cfg.synthetic, cfg.synthetic_res, split, n_blocks=cfg.synthetic_blocks) if cfg.synthetic > 0 else ds
@@ -356,6 +395,8 @@ def main():
             write_refined(d, split, rows, refined_rows)
         if ransac_rows:
             write_ransac(d, split, rows, ransac_rows, ransac_refined_rows)
+        if photo_rows:
+            write_photo_refined(d, split, photo_rows)
         if scene_rows:
             write_scenes(d, split, scene_rows)
         if scene_refined_rows:

@@ -889,6 +889,27 @@ int dreg_ngp_samples_grad(long n, const int* s_ray, const float* s_t, const floa
                           const float* g_rgb, const float* g_opacity, const float* g_depth, float render_step_size,
                           float* dirs, float* g_sigma, float* g_c, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- input gradients of a NeRF block's field
+ * (csrc/field_input_grad.hip; rule: DESIGN.md §3p).  dreg_ngp_points_input_grad: dreg_ngp_points_bwd's points, field and upstream gradients
+ * (g_sigma fp32 [n], g_rgb fp32 [n,3]; either may be null = zeros), with the parameters frozen -> grad_x fp32 [n,3] = dL/dx and grad_dir fp32
+ * [n,3] = dL/ddir (dirs is used as given, not renormalised), the straight-through gradient (fp16 roundings taken as identity).  Both are WRITTEN,
+ * not added; either may be null (not computed for the caller).  dL/dx_c is exactly 0 on an axis where the point is not strictly inside the model
+ * aabb (the encoding clamps there); dL/dh0 is 0 outside the aabb, the colour term is not.  A row without upstream gradient is written as zeros.
+ * Both outputs null: DREG_OK, nothing launched.  Both upstream pointers null: the outputs are written as zeros (a memset, no kernel).
+ * No workspace, no atomics: bit-identical between runs.  DREG_EINVAL, with nothing launched or written, for n < 0, a null required pointer
+ * or an aabb without extent; n == 0 returns DREG_OK first.
+ * dreg_ngp_samples_ray_grad: the sample list in CANONICAL order (ascending ray, then ord; s_ray int32 [n], s_t fp32 [n]) with its per-sample
+ * grad_x / grad_dir fp32 [n,3] -> grad_o fp32 [n_rays,3] = sum_k grad_x_k and grad_d fp32 [n_rays,3] = sum_k (t_k grad_x_k + grad_dir_k) over the
+ * ray's records in list order (x_k = o + t_k d with t_k constant, dirs_k = d).  One lane per ray finds its segment by bisection on s_ray (no
+ * offsets array from the host) and adds it in order: no atomics, bit-identical between runs.  Both outputs are written for all n_rays (zeros
+ * for a ray without records, n == 0 included).  DREG_EINVAL for n < 0, n_rays < 0, a null output, or a null list array with n > 0;
+ * n_rays == 0 returns DREG_OK first. */
+int dreg_ngp_points_input_grad(const float* x, const float* dirs, long n, const void* base16, const void* color16,
+                               const uint32_t* offset, const uint32_t* size, const uint32_t* res, const float* scale, const uint32_t* hashed,
+                               const float* model_aabb, const float* g_sigma, const float* g_rgb, float* grad_x, float* grad_dir, void* stream);
+int dreg_ngp_samples_ray_grad(long n, const int* s_ray, const float* s_t, const float* grad_x, const float* grad_dir, long n_rays,
+                              float* grad_o, float* grad_d, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- image metrics of rendered views
  * (csrc/image_metrics.hip; rule: DESIGN.md §3d) SSIM, MSE and PSNR of the reference's evaluate() (eval_ngp_nerf.py:24-31,214-229,
  * conerf/loss/ssim_torch.py) for N image pairs in one call.  pred, gt: fp32 [N,H,W,C], channel-last, contiguous, device; 1 <= C <= 4,
