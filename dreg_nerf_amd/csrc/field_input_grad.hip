@@ -1,97 +1,34 @@
 // Input gradients of a NeRF block's field (gfx950): dL/dx and dL/ddir at POINTS for two given upstream gradients, dL/dsigma [n] and dL/drgb [n,3],
 // with the parameters frozen, and their sums along rays.  The rule is DESIGN.md §3p; fp64 restatement: tests/field_input_grad_restatement.py.
 //
-// Point i, position x_i in the field's frame, direction d_i (used as given).  The forward is recomputed exactly as ngp_points_bwd_kernel
-// (field_train.hip) recomputes it, and the chain is that kernel's, the fp16 roundings taken as identity:
+// Point i, position x_i in the field's frame, direction d_i (used as given).  The forward is ngp_points_bwd_kernel's (field_train.hip): both
+// call field_point_forward of ngp_field_bwd.h; and the chain is that kernel's (fb_back, fb_store), the fp16 roundings taken as identity:
 //   dL/dh0 = g_sigma exp(min(h0 - 1, 15))  inside the model aabb, 0 outside          dL/do_c = g_rgb_c c (1 - c)
 //   d2 = relu'(h2) W3[0:3]^T do,  d1 = relu'(h1) W2^T d2,  dsh = W1[:, 0:16]^T d1,  dout = (dh0 | W1[:, 16:31]^T d1),
 //   dh = relu'(hd) W2d^T dout,  de = W1d^T dh
 // with two tails, one lane per point:
 //   dL/dd_c = sum_j dsh[j] dsh4_j/dd_c                         (the degree-4 polynomials of render_sh4_f16, differentiated in fp32)
 //   du_c = sum_l scale_l sum_corners (+-1)(w_a w_b)(de[2l] t_0 + de[2l+1] t_1),   dL/dx_c = du_c / (hi_c - lo_c) where 0 < u_c < 1, else exactly 0
-// (the corner loop of ngp_grad.hip).  The colour term does not depend on the aabb: a point outside on one axis keeps it on the other two.
+// (ngp_encoding_dx of ngp_field.h, which ngp_grad.hip calls too).  The colour term does not depend on the aabb: a point outside on one axis
+// keeps it on the other two.
 //
 // ngp_points_input_grad_kernel: one wave, 64 points per pass.  Nothing here needs an activation, only the three ReLU gates: each lane takes its
-// point's gates as 64-bit masks right after the forward (as ngp_grad.hip does), so the forward's tiles are dead when the chain starts and the
-// chain's fp32 tile sA [64 points][<= 64 units] lies over them.  LDS: two hidden tiles of 9,216 B (the encoding aliases the head of the first,
-// the colour net's input rows the head of the second, which is also the colour net's second hidden tile) + 1,280 B of outputs = 19,712 B.
-// A gate of another lane's point is fetched with a shuffle when the gated tile is stored.  No weight gradients: no slabs, no atomics, no
-// reduce pass, no workspace.
+// point's gates as 64-bit masks during the forward (ngp_relu_mask of ngp_field.h, as ngp_grad.hip does), so the forward's tiles are dead when
+// the chain starts and the chain's fp32 tile sA [64 points][<= 64 units] lies over them.  LDS: two hidden tiles of 9,216 B (the encoding
+// aliases the head of the first, the colour net's input rows the head of the second, which is also the colour net's second hidden tile) +
+// 1,280 B of outputs = 19,712 B.  A gate of another lane's point is fetched with a shuffle when the gated tile is stored (FbGateMask).  No
+// weight gradients: no slabs, no atomics, no reduce pass, no workspace.
 //
 // ngp_samples_ray_grad_kernel: one lane per ray.  The list is in canonical order (ascending ray, then ord), so a ray's records are one
 // contiguous segment; the lane finds its start by bisection on the ray column and adds the segment in order: deterministic by construction.
-#include "march.h"
+#include "ngp_field_bwd.h"
 #include "../../include/dreg_nerf.h"   // signature check of the entry points defined here
 
-constexpr int IG_AS = 68;              // row stride (floats) of sA (PB_AS of field_train.hip)
 constexpr int IG_TILE = 64 * NGP_HRS;  // one hidden tile
 
-struct InputGradArgs {
-    const float *x, *dirs;
-    long n;
-    const _Float16 *table, *w1, *w2, *cw1, *cw2, *cw3;
-    NgpLevels lv;
-    float model[6];
-    const float *g_sigma, *g_rgb;      // either may be null (zeros)
+struct InputGradArgs : FieldPointArgs {
     float *grad_x, *grad_dir;          // either may be null (not written)
 };
-
-// pb_back of field_train.hip, copied (that translation unit stays as it is):
-// dX[p][c0 + i] = sum_{k < 4 KS} sA[p][k] W[k][c0 + i], i < 16 NT, for the wave's 64 points (W: fp16 [.][ld], rows = the layer's outputs).
-// acc[pt][nt][r] = dX of point pt*16 + (lane >> 4)*4 + r, column c0 + nt*16 + (lane & 15).
-template <int KS, int NT>
-__device__ __forceinline__ void ig_back(f32x4_t (&acc)[4][NT], const float* sA, const _Float16* __restrict__ W, int ld, int c0, int lane)
-{
-    const int fr = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[pt][nt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int ks = 0; ks < KS; ++ks) {
-        float b[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b[nt] = (float)W[(ks * 4 + kq) * ld + c0 + nt * 16 + fr];
-#pragma unroll
-        for (int pt = 0; pt < 4; ++pt) {
-            const float av = sA[(pt * 16 + fr) * IG_AS + ks * 4 + kq];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[pt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[nt], acc[pt][nt], 0, 0, 0);
-        }
-    }
-}
-
-// acc -> sA columns 0 .. 16 NT - 1, gated by relu'(h): bit c of `gate`, the mask of the point's own lane (GATED false: no gate)
-template <int NT, bool GATED>
-__device__ __forceinline__ void ig_store(float* sA, const f32x4_t (&acc)[4][NT], unsigned long long gate, int lane)
-{
-    const int fr = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int p = pt * 16 + kq * 4 + r;
-            const unsigned long long m = GATED ? __shfl(gate, p, 64) : ~0ull;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int c = nt * 16 + fr;
-                sA[p * IG_AS + c] = ((m >> c) & 1ull) ? acc[pt][nt][r] : 0.f;
-            }
-        }
-}
-
-// bit j = the stored fp16 activation j of the lane's own row of the hidden tile is > 0
-__device__ __forceinline__ unsigned long long ig_gate(const char* sH, int lane)
-{
-    unsigned long long mask = 0ull;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const f16x8_t h = ldsfrag(sH, NGP_HRS, lane, k * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mask |= (h[j] > (_Float16)0.f) ? (1ull << (k * 8 + j)) : 0ull;
-    }
-    return mask;
-}
 
 // dL/dd_c = sum_j g[j] dsh4_j/dd_c: the polynomials of render_sh4_f16 differentiated term by term (g[0] meets the constant)
 __device__ __forceinline__ void ig_sh4_grad(const float (&d)[3], const float* g, float (&out)[3])
@@ -114,7 +51,7 @@ __global__ __launch_bounds__(64) void ngp_points_input_grad_kernel(InputGradArgs
     __shared__ __attribute__((aligned(16))) char smem[2 * IG_TILE];    // forward: two hidden tiles; chain: the fp32 tile sA over both
     __shared__ float sOut[64];
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
-    static_assert(64 * IG_AS * sizeof(float) <= 2 * IG_TILE, "sA must fit over the two hidden tiles");
+    static_assert(64 * FB_AS * sizeof(float) <= 2 * IG_TILE, "sA must fit over the two hidden tiles");
     char* sT0 = smem;                       // encoding rows (NGP_XRS) at its head, then the density hidden layer, then the colour net's first
     char* sT1 = smem + IG_TILE;             // colour input rows (NGP_XRS) at its head, then the colour net's second hidden layer
     float* sA = reinterpret_cast<float*>(smem);
@@ -124,97 +61,49 @@ __global__ __launch_bounds__(64) void ngp_points_input_grad_kernel(InputGradArgs
     for (long pb = (long)blockIdx.x * 64; pb < a.n; pb += (long)gridDim.x * 64) {
         const long p = pb + lane;
         const bool have = p < a.n;
-        float x[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f}, gs = 0.f, gc[3] = {0.f, 0.f, 0.f};
-        if (have) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { x[k] = a.x[p * 3 + k]; d[k] = a.dirs[p * 3 + k]; }
-            if (a.g_sigma) gs = a.g_sigma[p];
-            if (a.g_rgb) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) gc[k] = a.g_rgb[p * 3 + k];
-            }
-        }
         float gx[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
-        const bool live = gs != 0.f || gc[0] != 0.f || gc[1] != 0.f || gc[2] != 0.f;
-        if (__any(live)) {                                    // (no gradient arrives at these 64 points: zeros, without the forward)
-            // ---- the forward, sample for sample (ngp_field.h, march.h); lanes without a point take zero rows: every LDS row is written and finite
-            float u[3];
-            const bool inside_m = ngp_unit_cube(x, a.model, a.model + 3, 0, u) && have;
+        // ---- the forward, sample for sample; each lane takes its point's three ReLU gates as it goes (the density net's before the colour net
+        // overwrites its tile).  False: no gradient arrives at these 64 points: zeros, without the forward
+        FieldPoint fp;
+        unsigned long long m_hd = 0ull;
+        if (field_point_forward(a, p, have, sT0, sT0, sT1, sT0, sT1, sOut, sO, lane, fp, [&] { wave_sync(); m_hd = ngp_relu_mask(sT0, lane); })) {
+            const unsigned long long m_h1 = ngp_relu_mask(sT0, lane), m_h2 = ngp_relu_mask(sT1, lane);
+            const float (&dO)[3] = fp.dO;
+            const float dh0 = fp.dh0;
             bool open[3];                                     // the axis was not clamped: 0 < u_c < 1 before the clamp
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { const float ur = (x[c] - a.model[c]) / (a.model[3 + c] - a.model[c]); open[c] = ur > 0.f && ur < 1.f; }
-            unsigned long long m_hd, m_h1, m_h2;
-            {
-                _Float16* er = reinterpret_cast<_Float16*>(sT0 + lane * NGP_XRS);
-#pragma unroll 2
-                for (int l = 0; l < 16; ++l) {
-                    float f0 = 0.f, f1 = 0.f;
-                    if (have) ngp_level_features(a.table, a.lv, l, u, f0, f1);
-                    er[2 * l] = (_Float16)f0; er[2 * l + 1] = (_Float16)f1;
-                }
-                NgpDensityW dw;
-                ngp_load_density_w(dw, a.w1, a.w2, lane);
-                ngp_density_mlp(dw, sT0, sT0, lane, [&](int rb, const f32x4_t& ov) {      // ov[r] = output fr of point rb*16 + kq*4 + r
-                    if (fr == 0) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sOut[rb * 16 + kq * 4 + r] = (float)(_Float16)ov[r];
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) reinterpret_cast<_Float16*>(sT1 + (rb * 16 + kq * 4 + r) * NGP_XRS)[15 + fr] = (_Float16)ov[r];
-                    }
-                });
-                wave_sync();
-                m_hd = ig_gate(sT0, lane);
-                uint32_t sh2[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sh2[j] = 0u;
-                if (have) render_sh4_f16(d, sh2);
-                march_color_row(sT1, lane, sh2);
-                f16x8_t cw1f[4], cw3f[2];
-                march_load_color_w(cw1f, cw3f, a.cw1, a.cw3, lane);
-                march_color(sT1, sT0, sT1, sO, cw1f, a.cw2, cw3f, lane);      // the input rows are read in full before the second layer writes sT1
-                m_h1 = ig_gate(sT0, lane);
-                m_h2 = ig_gate(sT1, lane);
-            }
-            // ---- this lane's point: dL/d(colour pre-activation) and dL/dh0
-            float dO[3], dh0 = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float c = march_sigmoid_f16(sO[lane * 4 + ch]);
-                dO[ch] = gc[ch] * c * (1.f - c);
-            }
-            if (inside_m) dh0 = gs * __expf(fminf(sOut[lane] - 1.f, 15.f));
+            for (int c = 0; c < 3; ++c) { const float ur = (fp.x[c] - a.model[c]) / (a.model[3 + c] - a.model[c]); open[c] = ur > 0.f && ur < 1.f; }
             wave_sync();                                      // every lane has its gates: the tiles are dead, sA takes their place
-            float* rowA = sA + lane * IG_AS;
+            float* rowA = sA + lane * FB_AS;
             // d2 = relu'(h2) W3[0:3]^T dO (K = 4: column 3 of sA is 0)
 #pragma unroll
             for (int c = 0; c < 4; ++c) rowA[c] = c < 3 ? dO[c] : 0.f;
             wave_sync();
             {
                 f32x4_t acc[4][4];
-                ig_back<1, 4>(acc, sA, a.cw3, 64, 0, lane);
+                fb_back<1, 4>(acc, sA, a.cw3, 64, 0, lane);
                 wave_sync();
-                ig_store<4, true>(sA, acc, m_h2, lane);
+                fb_store<4>(sA, acc, FbGateMask{m_h2}, lane);
             }
             wave_sync();
             // d1 = relu'(h1) W2^T d2
             {
                 f32x4_t acc[4][4];
-                ig_back<16, 4>(acc, sA, a.cw2, 64, 0, lane);
+                fb_back<16, 4>(acc, sA, a.cw2, 64, 0, lane);
                 wave_sync();
-                ig_store<4, true>(sA, acc, m_h1, lane);
+                fb_store<4>(sA, acc, FbGateMask{m_h1}, lane);
             }
             wave_sync();
             // colour W1^T d1: columns 0..15 = dsh (kept in sA columns 16..31), columns 16..30 = dout[1..15] (sA columns 1..15); dout[0] = dh0
             {
                 f32x4_t acc[4][2];
-                ig_back<16, 2>(acc, sA, a.cw1, 32, 0, lane);
+                fb_back<16, 2>(acc, sA, a.cw1, 32, 0, lane);
                 wave_sync();
 #pragma unroll
                 for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float* row = sA + (pt * 16 + kq * 4 + r) * IG_AS;
+                        float* row = sA + (pt * 16 + kq * 4 + r) * FB_AS;
                         row[16 + fr] = acc[pt][0][r];
                         if (fr < 15) row[1 + fr] = acc[pt][1][r];
                     }
@@ -222,50 +111,27 @@ __global__ __launch_bounds__(64) void ngp_points_input_grad_kernel(InputGradArgs
             }
             wave_sync();
             // ---- the direction tail, one lane per point
-            if (live) ig_sh4_grad(d, rowA + 16, gd);
+            if (fp.live) ig_sh4_grad(fp.d, rowA + 16, gd);
             // dh = relu'(hd) W2d^T dout (K = 16: columns 16.. of sA are not read)
             {
                 f32x4_t acc[4][4];
-                ig_back<4, 4>(acc, sA, a.w2, 64, 0, lane);
+                fb_back<4, 4>(acc, sA, a.w2, 64, 0, lane);
                 wave_sync();
-                ig_store<4, true>(sA, acc, m_hd, lane);
+                fb_store<4>(sA, acc, FbGateMask{m_hd}, lane);
             }
             wave_sync();
             // de = W1d^T dh
             {
                 f32x4_t acc[4][2];
-                ig_back<16, 2>(acc, sA, a.w1, 32, 0, lane);
+                fb_back<16, 2>(acc, sA, a.w1, 32, 0, lane);
                 wave_sync();
-                ig_store<2, false>(sA, acc, 0ull, lane);
+                fb_store<2>(sA, acc, FbGateNone{}, lane);
             }
             wave_sync();
-            // ---- the position tail, one lane per point: the forward's corners again, with the hook of ngp_density_grad_kernel
+            // ---- the position tail, one lane per point: the encoding's derivative for the row de, as ngp_density_grad_kernel takes it
             if (dh0 != 0.f || dO[0] != 0.f || dO[1] != 0.f || dO[2] != 0.f) {      // (all zero: de is exactly 0, e.g. dL/dsigma alone at a point outside)
-                float du[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-                for (int l = 0; l < 16; ++l) {
-                    const float f0 = rowA[2 * l], f1 = rowA[2 * l + 1];
-                    const float sc = a.lv.scale[l];
-                    float w[3];                                      // the trilinear weights as ngp_level_corners forms them
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) { const float pos = u[c] * sc + 0.5f; w[c] = pos - floorf(pos); }
-                    const _Float16* tl = a.table + (size_t)a.lv.offset[l] * 2;
-                    float D[3] = {0.f, 0.f, 0.f};
-                    int corner = 0;                                  // ngp_level_corners calls the hook for corner 0..7 in order (unrolled: a constant)
-                    ngp_level_corners(a.lv, l, u, [&](size_t e, float) {
-                        union { uint32_t u32; _Float16 h[2]; } cv;
-                        cv.u32 = *reinterpret_cast<const uint32_t*>(tl + e);
-                        const float v = f0 * (float)cv.h[0] + f1 * (float)cv.h[1];
-                        const float wx = (corner & 1) ? w[0] : 1.f - w[0], wy = (corner & 2) ? w[1] : 1.f - w[1], wz = (corner & 4) ? w[2] : 1.f - w[2];
-                        const float a0 = (wy * wz) * v, a1 = (wx * wz) * v, a2 = (wx * wy) * v;
-                        D[0] += (corner & 1) ? a0 : -a0;
-                        D[1] += (corner & 2) ? a1 : -a1;
-                        D[2] += (corner & 4) ? a2 : -a2;
-                        ++corner;
-                    });
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) du[c] += sc * D[c];
-                }
+                float du[3];
+                ngp_encoding_dx(a.table, a.lv, fp.u, rowA, du);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) gx[c] = open[c] ? du[c] / (a.model[3 + c] - a.model[c]) : 0.f;
             }
@@ -320,24 +186,14 @@ int dreg_ngp_points_input_grad(const float* x, const float* dirs, long n, const 
 {
     if (n < 0) return DREG_EINVAL;
     if (n == 0) return DREG_OK;
-    if (!x || !dirs || !base16 || !color16 || !offset || !size || !res || !scale || !hashed || !model_aabb) return DREG_EINVAL;
-    for (int k = 0; k < 3; ++k)
-        if (!(model_aabb[3 + k] > model_aabb[k])) return DREG_EINVAL;
+    InputGradArgs a;
+    if (field_fill_points(a, x, dirs, n, base16, color16, offset, size, res, scale, hashed, model_aabb, g_sigma, g_rgb) != DREG_OK) return DREG_EINVAL;
     if (!grad_x && !grad_dir) return DREG_OK;        // nothing to write: nothing is launched
     if (!g_sigma && !g_rgb) {                        // both upstream gradients are zero: the outputs are WRITTEN, as zeros, without a kernel
         if (grad_x && hipMemsetAsync(grad_x, 0, (size_t)n * 3 * sizeof(float), (hipStream_t)stream) != hipSuccess) return DREG_ELAUNCH;
         if (grad_dir && hipMemsetAsync(grad_dir, 0, (size_t)n * 3 * sizeof(float), (hipStream_t)stream) != hipSuccess) return DREG_ELAUNCH;
         return DREG_OK;
     }
-    const _Float16* b16 = (const _Float16*)base16;
-    const _Float16* c16 = (const _Float16*)color16;
-    InputGradArgs a;
-    a.x = x; a.dirs = dirs; a.n = n;
-    a.table = b16 + 3072; a.w1 = b16; a.w2 = b16 + 2048;
-    a.cw1 = c16; a.cw2 = c16 + 2048; a.cw3 = c16 + 6144;
-    ngp_fill_levels(a.lv, offset, size, res, scale, hashed);
-    for (int k = 0; k < 6; ++k) a.model[k] = model_aabb[k];
-    a.g_sigma = g_sigma; a.g_rgb = g_rgb;
     a.grad_x = grad_x; a.grad_dir = grad_dir;
     long waves = (n + 63) / 64;
     if (waves > (1l << 20)) waves = 1l << 20;        // beyond 2^26 points a workgroup takes more than one pass

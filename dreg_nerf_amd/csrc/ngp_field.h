@@ -2,6 +2,7 @@
 // encoding of a point (NGPradianceField.query_density, conerf/radiance_fields/ngp.py:148-176: HashGrid L=16 F=2) and the 32 -> 64 -> 16
 // density MLP on fp16 MFMA (16x16x32) through LDS.  The dense query (ngp.hip), the ray marchers (march.h: visibility.hip, render.hip) and
 // the training backward (render_train.hip), which re-marches every ray, must agree bit for bit: they all call the functions below.
+// The kernels that differentiate the field by position (ngp_grad.hip, field_input_grad.hip) share ngp_relu_mask and ngp_encoding_dx.
 // Table and weights are fp16, trilinear interpolation in fp32 rounded to fp16, layer inputs fp16, accumulation fp32.
 #pragma once
 #include "common.h"
@@ -128,7 +129,54 @@ __device__ __forceinline__ void ngp_level_features(const _Float16* __restrict__ 
     ngp_level_corners(lv, l, u, [&](size_t e, float wt) { ngp_corner_accumulate(tl, e, wt, f0, f1); });
 }
 
+// The encoding's derivative by position for a row f[32] of gradients by the 32 encoded features (ngp_grad.hip, field_input_grad.hip):
+//   du_c = sum_l scale_l sum_corners (s_c w_a w_b) (f[2l] t_0 + f[2l+1] t_1),   s_c = +-1 by the corner's side on axis c, w_a, w_b the trilinear
+// weights of the other two axes, t the corner's two table entries.  The corner loop of every level runs again with a hook that accumulates the
+// three derivatives: the same gathers as the forward, no atomics.  The caller scales by 1 / (hi_c - lo_c) and masks by its own rule.
+__device__ __forceinline__ void ngp_encoding_dx(const _Float16* __restrict__ table, const NgpLevels& lv, const float (&u)[3], const float* f, float (&du)[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) du[c] = 0.f;
+#pragma unroll 1
+    for (int l = 0; l < 16; ++l) {
+        const float f0 = f[2 * l], f1 = f[2 * l + 1];
+        const float sc = lv.scale[l];
+        float w[3];                                      // the trilinear weights as ngp_level_corners forms them
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { const float pos = u[c] * sc + 0.5f; w[c] = pos - floorf(pos); }
+        const _Float16* tl = table + (size_t)lv.offset[l] * 2;
+        float D[3] = {0.f, 0.f, 0.f};
+        int corner = 0;                                  // ngp_level_corners calls the hook for corner 0..7 in order (unrolled: a constant)
+        ngp_level_corners(lv, l, u, [&](size_t e, float) {
+            union { uint32_t u32; _Float16 h[2]; } cv;
+            cv.u32 = *reinterpret_cast<const uint32_t*>(tl + e);
+            const float v = f0 * (float)cv.h[0] + f1 * (float)cv.h[1];
+            const float wx = (corner & 1) ? w[0] : 1.f - w[0], wy = (corner & 2) ? w[1] : 1.f - w[1], wz = (corner & 4) ? w[2] : 1.f - w[2];
+            const float a0 = (wy * wz) * v, a1 = (wx * wz) * v, a2 = (wx * wy) * v;
+            D[0] += (corner & 1) ? a0 : -a0;
+            D[1] += (corner & 2) ? a1 : -a1;
+            D[2] += (corner & 4) ? a2 : -a2;
+            ++corner;
+        });
+#pragma unroll
+        for (int c = 0; c < 3; ++c) du[c] += sc * D[c];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ density MLP
+// The ReLU mask of a lane's own row of a hidden tile (64 fp16 units, stride NGP_HRS): bit j = the stored activation j is > 0.
+__device__ __forceinline__ unsigned long long ngp_relu_mask(const char* sH, int lane)
+{
+    unsigned long long mask = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const f16x8_t h = ldsfrag(sH, NGP_HRS, lane, k * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mask |= (h[j] > (_Float16)0.f) ? (1ull << (k * 8 + j)) : 0ull;
+    }
+    return mask;
+}
+
 // The density MLP's weights as MFMA operands, held in registers: w1 fp16 [64][32], w2 fp16 [16][64].
 struct NgpDensityW { f16x8_t w1f[4], w2f[2]; };
 __device__ __forceinline__ void ngp_load_density_w(NgpDensityW& w, const _Float16* w1, const _Float16* w2, int lane)

@@ -7,8 +7,8 @@
 //   weights of the other two axes, t the corner's two table entries;   grad_c = sigma du_c / (hi_c - lo_c), zero outside the aabb.
 // One point per lane, one wave per 64 points and per workgroup, as ngp_density_kernel.  f = W1^T g comes from LDS-staged weights (every lane reads
 // the same row: a broadcast), 32 accumulators per lane; it then goes to the lane's own row of the hidden tile, from where the level loop reads two
-// values per level.  The corner loop of every level runs a second time with a hook that accumulates the three derivatives: the same gathers as
-// the forward, no atomics.
+// values per level.  The ReLU mask and the encoding's derivative (the corner loop of every level, run a second time with a hook that accumulates
+// the three derivatives) are ngp_field.h's ngp_relu_mask and ngp_encoding_dx, which the input gradients of field_input_grad.hip call as well.
 #include "ngp_field.h"
 
 __global__ __launch_bounds__(64) void ngp_density_grad_kernel(const float* __restrict__ x, const _Float16* __restrict__ table,
@@ -55,14 +55,7 @@ __global__ __launch_bounds__(64) void ngp_density_grad_kernel(const float* __res
     });
     wave_sync();
     const float sigma = __expf(sD[lane] - 1.f) * (inside ? 1.f : 0.f);
-    // ReLU mask from the lane's own row of the hidden tile: bit j = the stored fp16 h_j > 0
-    unsigned long long mask = 0ull;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const f16x8_t h = ldsfrag(sH, HRS, lane, k * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mask |= (h[j] > (_Float16)0.f) ? (1ull << (k * 8 + j)) : 0ull;
-    }
+    const unsigned long long mask = ngp_relu_mask(sH, lane);      // bit j = the stored fp16 h_j > 0
     // f = W1^T g: products of two fp16 values are exact in fp32, the 64 additions round
     float f[32];
 #pragma unroll
@@ -81,31 +74,8 @@ __global__ __launch_bounds__(64) void ngp_density_grad_kernel(const float* __res
     float* fr_row = reinterpret_cast<float*>(sH + lane * HRS);
 #pragma unroll
     for (int i = 0; i < 32; ++i) fr_row[i] = f[i];
-    float du[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int l = 0; l < 16; ++l) {
-        const float f0 = fr_row[2 * l], f1 = fr_row[2 * l + 1];
-        const float sc = lv.scale[l];
-        float w[3];                                      // the trilinear weights as ngp_level_corners forms them
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { const float pos = u[c] * sc + 0.5f; w[c] = pos - floorf(pos); }
-        const _Float16* tl = table + (size_t)lv.offset[l] * 2;
-        float D[3] = {0.f, 0.f, 0.f};
-        int corner = 0;                                  // ngp_level_corners calls the hook for corner 0..7 in order (unrolled: a constant)
-        ngp_level_corners(lv, l, u, [&](size_t e, float) {
-            union { uint32_t u32; _Float16 h[2]; } cv;
-            cv.u32 = *reinterpret_cast<const uint32_t*>(tl + e);
-            const float v = f0 * (float)cv.h[0] + f1 * (float)cv.h[1];
-            const float wx = (corner & 1) ? w[0] : 1.f - w[0], wy = (corner & 2) ? w[1] : 1.f - w[1], wz = (corner & 4) ? w[2] : 1.f - w[2];
-            const float a0 = (wy * wz) * v, a1 = (wx * wz) * v, a2 = (wx * wy) * v;
-            D[0] += (corner & 1) ? a0 : -a0;
-            D[1] += (corner & 2) ? a1 : -a1;
-            D[2] += (corner & 4) ? a2 : -a2;
-            ++corner;
-        });
-#pragma unroll
-        for (int c = 0; c < 3; ++c) du[c] += sc * D[c];
-    }
+    float du[3];
+    ngp_encoding_dx(table, lv, u, fr_row, du);
     if (p < Np) {
         density[p] = sigma;
 #pragma unroll

@@ -2,10 +2,9 @@
 // samples down, and the kernel that turns per-ray upstream gradients (colour, opacity, depth) into the per-sample dL/dsigma and dL/dc that
 // dreg_ngp_points_bwd (field_train.hip) takes.  fp64 restatement: tests/render_samples_restatement.py.
 //
-// ngp_render_samples_kernel is ngp_render_kernel (render.hip) sample for sample: the same march.h helpers in the same order (march_take over
-// the queue, render_ray_interval with the jitter, march_advance, march_density<true>, the composite step, march_color, march_sigmoid_f16), so
-// rgb, opacity, depth and n_samples are those of dreg_ngp_render_train bit for bit.  Per survivor k of a ray it records, fp32 as the lane holds
-// them (nothing is recomputed):
+// The forward is ngp_render_kernel<true> of render_loop.h: the loop of dreg_ngp_render_train itself, instantiated with the record store, so
+// rgb, opacity, depth and n_samples are those of dreg_ngp_render_train bit for bit by construction.  Per survivor k of a ray it records, fp32 as
+// the lane holds them (nothing is recomputed):
 //   ray, ord        the ray and the number of earlier survivors of it
 //   t, x[3]         t_mid and the position march_advance returned
 //   T_next, w       T_s after the sample (T_{k+1}) and the weight
@@ -21,162 +20,10 @@
 //   dL/dsigma_k = dt ( sum_ch g_C[ch] (T_{k+1} c_k[ch] - (C[ch] - P_k[ch]))  +  g_O (1 - O)  +  g_D (T_{k+1} t_k - (D - Pd_k)) )
 // (dw_k/dsigma_k = dt T_{k+1}, dw_j/dsigma_k = -dt w_j for j > k, dO/dsigma_k = dt T_end = dt (1 - O); the colour term is §3c's, in the order
 // ngp_render_bwd_kernel evaluates it), and dirs_k = viewdirs[ray]: with x these are dreg_ngp_points_bwd's four inputs.
-#include "march.h"
+#include "render_loop.h"
 #include "../../include/dreg_nerf.h"   // signature check of the entry points defined here
 
-struct SampleList {
-    int *ray, *ord;             // [capacity]
-    float *t, *x;               // [capacity], [capacity,3]
-    float *T_next, *w;          // [capacity]
-    float *c, *P, *Pd;          // [capacity,3], [capacity,3], [capacity]
-};
-
-struct RenderSamplesArgs : MarchBlock {       // RenderArgs of render.hip, then the list
-    const float* origins;
-    const float* dirs;
-    const float* jitter;
-    long n_rays;
-    float eps;
-    float bkgd[3];
-    long pass_bound;
-    float *rgb, *opacity, *depth;
-    unsigned long long* n_samples;
-    unsigned long long* queue;
-    unsigned long long* slots;  // the list's slot counter: ends at the true number of survivors
-    unsigned long long capacity;
-    SampleList list;
-};
-
 DREG_KNOB(int, g_render_samples_waves, 2048);     // tuning (include/dreg_nerf_probe.h): one-wave workgroups of the launch; same per-ray results and same sorted list at every width
-
-__device__ __forceinline__ void samples_write_ray(const RenderSamplesArgs& a, long ray, const float (&acc)[3], float opac, float dep)
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.rgb[ray * 3 + k] = acc[k] + a.bkgd[k] * (1.f - opac);
-    a.opacity[ray] = opac;
-    a.depth[ray] = dep;
-}
-
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ngp_render_samples_kernel(RenderSamplesArgs a)
-{
-    __shared__ __attribute__((aligned(16))) char sX[64 * NGP_XRS];
-    __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];
-    __shared__ float sOut[64];
-    __shared__ __attribute__((aligned(16))) float sO[64 * 4];
-    __shared__ uint32_t sCoarse[1024];
-    const int lane = threadIdx.x;
-    march_load_coarse(sCoarse, a, lane);
-    __syncthreads();
-    MarchGrid g;
-    march_grid(g, a, sCoarse);
-    NgpDensityW dw;
-    ngp_load_density_w(dw, a.w1, a.w2, lane);
-    f16x8_t cw1f[4], cw3f[2];
-    march_load_color_w(cw1f, cw3f, a.cw1, a.cw3, lane);
-    MarchQueue queue = {a.queue};
-    MarchQueue slots = {a.slots};
-
-    // per-lane ray state (ngp_render_kernel's, and ord: the survivors of this ray so far)
-    bool active = false, exhausted = false;
-    long ray = 0;
-    int n = 0, n_lim = 0, ord = 0;
-    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f}, tmin = 0.f, tmax = 0.f;
-    float T_all = 1.f, T_s = 1.f, acc[3] = {0.f, 0.f, 0.f}, opac = 0.f, dep = 0.f;
-    uint32_t sh2[8];
-    unsigned long long my_samples = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sh2[j] = 0u;
-
-    bool finished = false;
-    for (long it = 0; it < a.pass_bound; ++it) {
-        // ---- refill: lanes without a ray take the next ones from the queue; rays that miss the aabb are written at once
-        for (int tries = 0; tries < 1024; ++tries) {
-            const bool need = !active && !exhausted;
-            unsigned long long r = 0;
-            if (!march_take(queue, need, lane, r)) break;
-            if (need) {
-                if (r >= (unsigned long long)a.n_rays) exhausted = true;
-                else {
-                    ray = (long)r;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) { o[k] = a.origins[ray * 3 + k]; d[k] = a.dirs[ray * 3 + k]; }
-                    const bool hit = render_ray_interval(o, d, a.scene, a.near, a.far, tmin, tmax);
-                    tmin += a.jitter[ray] * a.dt;
-                    const float acc0[3] = {0.f, 0.f, 0.f};
-                    if (!hit || !(tmin < tmax)) samples_write_ray(a, ray, acc0, 0.f, 0.f);
-                    else {
-                        active = true; n = 0; ord = 0; T_all = 1.f; T_s = 1.f; opac = 0.f; dep = 0.f;
-                        acc[0] = acc[1] = acc[2] = 0.f;
-                        n_lim = (int)fminf(ceilf((tmax - tmin) / a.dt) + 1.f, (float)a.n_max);
-                        render_sh4_f16(d, sh2);
-                    }
-                }
-            }
-        }
-        if (!__any(active)) {
-            if (__all(exhausted)) { finished = true; break; }
-            continue;
-        }
-        // ---- advance every live ray to its next lattice sample inside an occupied cell
-        float x[3] = {0.f, 0.f, 0.f}, tm = 0.f;
-        const bool was_active = active;
-        if (active && n >= n_lim) active = false;
-        const bool have = march_advance(g, o, d, tmin, tmax, a.dt, n, active, x, &tm, 4096);
-        if (was_active && !active) samples_write_ray(a, ray, acc, opac, dep);
-        if (!__any(have)) continue;
-        // ---- density of the wave's samples; their features land in the colour net's input rows
-        const bool inside_m = march_density<true>(have, x, a.model, a.lv, a.table, dw, sX, sH, sOut, lane);
-        bool surv = false;
-        float w = 0.f;
-        if (have) {
-            // ngp_render_kernel's sample step, operation for operation (march_composite and march_color_row with omega = 1)
-            const float sigma = inside_m ? __expf(sOut[lane] - 1.f) : 0.f;
-            const float alpha = 1.f - __expf(-sigma * a.dt);
-            surv = T_all >= a.eps && (a.alpha_thre <= 0.f || alpha >= a.alpha_thre);
-            T_all *= (1.f - alpha);
-            ++n;
-            if (surv) {
-                w = alpha * T_s;
-                T_s *= (1.f - alpha);
-                uint32_t* xr = reinterpret_cast<uint32_t*>(sX + lane * NGP_XRS);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xr[j] = sh2[j];
-                reinterpret_cast<_Float16*>(sX + lane * NGP_XRS)[31] = (_Float16)1.f;
-            }
-        }
-        if (__any(surv)) {
-            march_color(sX, sH, sH, sO, cw1f, a.cw2, cw3f, lane);
-            // ---- the survivors' slots: one returning atomic for the wave, consecutive in lane order
-            unsigned long long slot = 0;
-            (void)march_take(slots, surv, lane, slot);
-            if (surv) {
-                const float4 pre = *reinterpret_cast<const float4*>(sO + lane * 4);
-                const float pv[3] = {pre.x, pre.y, pre.z};
-                float c[3];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) { c[ch] = march_sigmoid_f16(pv[ch]); acc[ch] += w * c[ch]; }
-                opac += w;
-                dep += w * tm;
-                ++my_samples;
-                if (slot < a.capacity) {
-                    const size_t s = (size_t)slot;
-                    a.list.ray[s] = (int)ray; a.list.ord[s] = ord;
-                    a.list.t[s] = tm; a.list.T_next[s] = T_s; a.list.w[s] = w; a.list.Pd[s] = dep;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) { a.list.x[s * 3 + k] = x[k]; a.list.c[s * 3 + k] = c[k]; a.list.P[s * 3 + k] = acc[k]; }
-                }
-                ++ord;
-            }
-        }
-        if (have && T_all < a.eps) { active = false; samples_write_ray(a, ray, acc, opac, dep); }
-        wave_sync();
-    }
-    unsigned long long tot = my_samples;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
-    if (lane == 0 && tot) atomicAdd(a.n_samples, tot);
-    if (!finished && lane == 0) atomicOr(a.queue, 1ull << 63);
-}
 
 struct SamplesGradArgs {
     long n;
@@ -230,23 +77,11 @@ int dreg_ngp_render_train_samples(const float* origins, const float* viewdirs, c
     if (n_rays == 0) return DREG_OK;
     if (capacity < 0) return DREG_EINVAL;
     if (capacity > 0 && (!s_ray || !s_ord || !s_t || !s_x || !s_T_next || !s_w || !s_c || !s_P || !s_Pd)) return DREG_EINVAL;
-    if (!origins || !viewdirs || !jitter || !bkgd || !rgb || !opacity || !depth || !n_samples || !queue || !slots) return DREG_EINVAL;
-    RenderSamplesArgs a;
-    if (march_fill_block(a, binary, rx, ry, rz, coarse_bits, table, w1, w2, true, cw1, cw2, cw3, offset, size, res, scale, hashed,
-                         roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, true) != DREG_OK)
-        return DREG_EINVAL;
-    a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
-    a.eps = early_stop_eps;
-    for (int k = 0; k < 3; ++k) a.bkgd[k] = bkgd[k];
-    a.pass_bound = march_pass_bound(n_rays, (double)(a.n_max + 2));
-    a.rgb = rgb; a.opacity = opacity; a.depth = depth; a.n_samples = n_samples; a.queue = (unsigned long long*)queue;
-    a.slots = (unsigned long long*)slots; a.capacity = (unsigned long long)capacity;
-    a.list = SampleList{s_ray, s_ord, s_t, s_x, s_T_next, s_w, s_c, s_P, s_Pd};
-    long waves = (n_rays + 63) / 64;
-    if (waves > g_render_samples_waves) waves = g_render_samples_waves;
-    hipLaunchKernelGGL(ngp_render_samples_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
-    DREG_LAUNCH_CHECK();
-    return DREG_OK;
+    if (!jitter || !slots) return DREG_EINVAL;
+    const RenderRecord rec = {(unsigned long long*)slots, (unsigned long long)capacity, SampleList{s_ray, s_ord, s_t, s_x, s_T_next, s_w, s_c, s_P, s_Pd}};
+    return render_launch<true>(origins, viewdirs, jitter, n_rays, binary, rx, ry, rz, coarse_bits, table, w1, w2, cw1, cw2, cw3, offset, size, res, scale, hashed,
+                               roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, early_stop_eps, bkgd,
+                               rgb, opacity, depth, n_samples, queue, g_render_samples_waves, &rec, stream);
 }
 
 // The per-sample gradients of n records (any order) for the per-ray upstream gradients g_rgb [n_rays,3], g_opacity [n_rays], g_depth [n_rays]

@@ -16,16 +16,10 @@
 //   * per wave, on MFMA (v_mfma_f32_16x16x4_f32, fp32): the weight gradients as sample-sum outer products (K = the wave's 64 samples), added into
 //     the chunk's own fp32 slab in global memory (the wave owns it: plain loads and stores);
 //   * per lane: the hash-table gradient, 16 levels x 8 corners x 2 fp32 global atomic adds (order free).
-// ngp_bwd_reduce_kernel then sums the slabs in chunk order: the MLP weight gradients are bit-identical across runs and launch widths.
-#include "march.h"
+// fb_reduce then sums the slabs in chunk order: the MLP weight gradients are bit-identical across runs and launch widths.  The slab layout, the
+// chunk rule, the outer product (fb_outer) and the reduce are ngp_field_bwd.h's, shared with the point backward (field_train.hip).
+#include "ngp_field_bwd.h"
 #include "../../include/dreg_nerf.h"   // signature check of the entry points defined here
-
-// one slab = the five weight matrices in parameter order: density W1 [64][32], W2 [16][64] (= mlp_base.params[0:3072]), colour W1 [64][32],
-// W2 [64][64], W3 [16][64] (= color_mlp.params)
-constexpr int BWD_SLAB = 10240;
-constexpr int BWD_OFF_D1 = 0, BWD_OFF_D2 = 2048, BWD_OFF_C1 = 3072, BWD_OFF_C2 = 5120, BWD_OFF_C3 = 9216;
-constexpr long BWD_MAX_CHUNKS = 2048;
-constexpr int BWD_AS = 68;             // row stride (floats) of the wave's fp32 delta tile sA [64 samples][<= 64]
 
 struct RenderBwdArgs : MarchBlock {    // the forward's block (march.h), then the launch's own
     const float *origins, *dirs, *jitter;
@@ -35,40 +29,21 @@ struct RenderBwdArgs : MarchBlock {    // the forward's block (march.h), then th
     long pass_bound;                   // passes per chunk: chunk_rays * (n_max + 2) + 64 (march_pass_bound)
     const float *rgb, *grad_rgb;       // forward rgb (with background) and dL/drgb, fp32 [N,3]
     float* grad_table;                 // fp32 [entries][2], accumulated with atomics
-    float* slabs;                      // fp32 [n_chunks][BWD_SLAB], zeroed by the entry point
+    float* slabs;                      // fp32 [n_chunks][FB_SLAB], zeroed by the entry point
     long chunk_rays;
     int n_chunks;
     unsigned int* queue;               // chunk counter, zeroed by the entry point
 };
 
+constexpr size_t BWD_LEAD = (size_t)FB_SLAB * sizeof(float);      // the workspace begins with wf
+
 DREG_KNOB(int, g_render_bwd_waves, 2048);     // tuning (include/dreg_nerf_probe.h): one-wave workgroups of the backward launch; same results at every width
 
-static long bwd_chunk_rays(long n_rays)
-{
-    const long waves = (n_rays + 63) / 64;
-    return 64 * ((waves + BWD_MAX_CHUNKS - 1) / BWD_MAX_CHUNKS);
-}
-
-// W[m][n] += sum_s sA[s][m] X(s, n) over the wave's 64 samples, for the MT x NT 16x16 tiles of W (row stride ld) in the chunk's slab.  X(s, n) is
-// read from fp16 LDS rows and masked by sLive (rows of samples that did not survive are not read: they may hold anything).
+// the weight gradient of a layer over the surviving samples, the tile loops unrolled in full
 template <int MT, int NT>
 __device__ __forceinline__ void bwd_outer(float* slab, int ld, const float* sA, const char* sXin, int xrs, const float* sLive, int lane)
 {
-    const int fr = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-            for (int kk = 0; kk < 16; ++kk) {
-                const int s = kk * 4 + kq;
-                const float xv = sLive[s] != 0.f ? (float)reinterpret_cast<const _Float16*>(sXin + s * xrs)[nt * 16 + fr] : 0.f;
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sA[s * BWD_AS + mt * 16 + fr], xv, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) slab[(mt * 16 + kq * 4 + r) * ld + nt * 16 + fr] += acc[r];    // W[mt*16 + kq*4 + r][nt*16 + fr]
-        }
+    fb_outer<MT, NT, true, true>(slab, ld, sA, sXin, xrs, sLive, lane);
 }
 
 __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
@@ -77,7 +52,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
     __shared__ __attribute__((aligned(16))) char sH[64 * NGP_HRS];     // density hidden layer
     __shared__ __attribute__((aligned(16))) char sH1[64 * NGP_HRS];    // colour hidden layers
     __shared__ __attribute__((aligned(16))) char sH2[64 * NGP_HRS];
-    __shared__ __attribute__((aligned(16))) float sA[64 * BWD_AS];
+    __shared__ __attribute__((aligned(16))) float sA[64 * FB_AS];
     __shared__ float sOut[64], sLive[64];
     __shared__ __attribute__((aligned(16))) float sO[64 * 4];
     __shared__ uint32_t sCoarse[1024];
@@ -93,20 +68,18 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
     ngp_load_density_w(dw, a.w1, a.w2, lane);
     f16x8_t cw1f[4], cw3f[2];
     march_load_color_w(cw1f, cw3f, a.cw1, a.cw3, lane);
-    const float* wd1 = a.wf + BWD_OFF_D1;
-    const float* wd2 = a.wf + BWD_OFF_D2;
-    const float* wc1 = a.wf + BWD_OFF_C1;
-    const float* wc2 = a.wf + BWD_OFF_C2;
-    const float* wc3 = a.wf + BWD_OFF_C3;
+    const float* wd1 = a.wf + FB_OFF_D1;
+    const float* wd2 = a.wf + FB_OFF_D2;
+    const float* wc1 = a.wf + FB_OFF_C1;
+    const float* wc2 = a.wf + FB_OFF_C2;
+    const float* wc3 = a.wf + FB_OFF_C3;
 
     for (;;) {
-        unsigned int chunk = 0;
-        if (lane == 0) chunk = atomicAdd(a.queue, 1u);
-        chunk = __shfl(chunk, 0, 64);
+        const unsigned int chunk = fb_next_chunk(a.queue, lane);
         if (chunk >= (unsigned int)a.n_chunks) break;
         const long r0 = (long)chunk * a.chunk_rays;
         const long r1 = min(a.n_rays, r0 + a.chunk_rays);
-        float* slab = a.slabs + (size_t)chunk * BWD_SLAB;
+        float* slab = a.slabs + (size_t)chunk * FB_SLAB;
         MarchChunk own = {r0};
         bool active = false, exhausted = false;
         long ray = 0;
@@ -175,12 +148,12 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                     }
                     dh0 = inside_m ? a.dt * dsig * __expf(fminf(h0 - 1.f, 15.f)) : 0.f;
                 }
-                float* rowA = sA + lane * BWD_AS;
+                float* rowA = sA + lane * FB_AS;
                 // colour W3 (rows 0..2 of 16): dW3[c][i] += dO[c] h2[i]
 #pragma unroll
                 for (int c = 0; c < 16; ++c) rowA[c] = c < 3 ? dO[c] : 0.f;
                 wave_sync();
-                bwd_outer<1, 4>(slab + BWD_OFF_C3, 64, sA, sH2, NGP_HRS, sLive, lane);
+                bwd_outer<1, 4>(slab + FB_OFF_C3, 64, sA, sH2, NGP_HRS, sLive, lane);
                 const _Float16* h2 = reinterpret_cast<const _Float16*>(sH2 + lane * NGP_HRS);
                 const _Float16* h1 = reinterpret_cast<const _Float16*>(sH1 + lane * NGP_HRS);
                 float d2[64];
@@ -194,7 +167,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
                 for (int j = 0; j < 64; ++j) rowA[j] = d2[j];
                 wave_sync();
-                bwd_outer<4, 4>(slab + BWD_OFF_C2, 64, sA, sH1, NGP_HRS, sLive, lane);
+                bwd_outer<4, 4>(slab + FB_OFF_C2, 64, sA, sH1, NGP_HRS, sLive, lane);
                 float d1[64];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) d1[i] = 0.f;
@@ -211,7 +184,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
                 for (int i = 0; i < 64; ++i) rowA[i] = d1[i];
                 wave_sync();
-                bwd_outer<4, 2>(slab + BWD_OFF_C1, 32, sA, sX, NGP_XRS, sLive, lane);
+                bwd_outer<4, 2>(slab + FB_OFF_C1, 32, sA, sX, NGP_XRS, sLive, lane);
                 float dout[16];
                 dout[0] = dh0;
 #pragma unroll
@@ -227,7 +200,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) rowA[k] = dout[k];
                 wave_sync();
-                bwd_outer<1, 4>(slab + BWD_OFF_D2, 64, sA, sH, NGP_HRS, sLive, lane);
+                bwd_outer<1, 4>(slab + FB_OFF_D2, 64, sA, sH, NGP_HRS, sLive, lane);
                 const _Float16* hd = reinterpret_cast<const _Float16*>(sH + lane * NGP_HRS);
                 float dh[64];
 #pragma unroll
@@ -271,7 +244,7 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
                 }
                 wave_sync();
                 // density W1: dW1[i][k] += dh[i] enc[k]
-                bwd_outer<4, 2>(slab + BWD_OFF_D1, 32, sA, sX, NGP_XRS, sLive, lane);
+                bwd_outer<4, 2>(slab + FB_OFF_D1, 32, sA, sX, NGP_XRS, sLive, lane);
             }
             if (have && T_all < a.eps) active = false;           // transmittance below early_stop_eps: the ray ends
             wave_sync();
@@ -279,22 +252,12 @@ __global__ __launch_bounds__(64) void ngp_render_bwd_kernel(RenderBwdArgs a)
     }
 }
 
-// grad[e] += sum over chunks (in chunk order) of slab[c][e]: base = mlp_base.params[0:3072] gradient, color = color_mlp.params gradient
-__global__ void ngp_bwd_reduce_kernel(const float* __restrict__ slabs, int n_chunks, float* __restrict__ grad_base, float* __restrict__ grad_color)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= BWD_SLAB) return;
-    float s = 0.f;
-    for (int c = 0; c < n_chunks; ++c) s += slabs[(size_t)c * BWD_SLAB + e];
-    if (e < BWD_OFF_C1) grad_base[e] += s;
-    else grad_color[e - BWD_OFF_C1] += s;
-}
-
+// fp32 copies of the five weight matrices in slab layout, from the fp16 inference copies
 __global__ void ngp_bwd_weights_kernel(const _Float16* __restrict__ base16, const _Float16* __restrict__ col16, float* __restrict__ wf)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= BWD_SLAB) return;
-    wf[e] = e < BWD_OFF_C1 ? (float)base16[e] : (float)col16[e - BWD_OFF_C1];
+    if (e >= FB_SLAB) return;
+    wf[e] = e < FB_OFF_C1 ? (float)base16[e] : (float)col16[e - FB_OFF_C1];
 }
 
 // torch.optim.Adam (single-tensor arithmetic, no weight decay) + the fp16 inference copy + a zeroed gradient, in one pass
@@ -314,23 +277,12 @@ __global__ void ngp_adam_kernel(float* __restrict__ p, float* __restrict__ g, fl
     }
 }
 
-static int bwd_layout(long n_rays, long* chunk_rays, int* n_chunks, size_t* slab_off, size_t* queue_off, size_t* total)
-{
-    if (n_rays <= 0) return DREG_EINVAL;
-    *chunk_rays = bwd_chunk_rays(n_rays);
-    *n_chunks = (int)((n_rays + *chunk_rays - 1) / *chunk_rays);
-    *slab_off = (size_t)BWD_SLAB * sizeof(float);
-    *queue_off = *slab_off + (size_t)*n_chunks * BWD_SLAB * sizeof(float);
-    *total = *queue_off + 256;
-    return DREG_OK;
-}
-
 extern "C" {
 
 size_t dreg_ngp_render_bwd_workspace_bytes(long n_rays)
 {
-    long cr; int nc; size_t so, qo, tot;
-    return bwd_layout(n_rays, &cr, &nc, &so, &qo, &tot) == DREG_OK ? tot : 0;
+    FbLayout w;
+    return fb_layout(n_rays, BWD_LEAD, w) == DREG_OK ? w.total : 0;
 }
 
 int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float* jitter, long n_rays, const uint8_t* binary, int rx, int ry, int rz,
@@ -344,33 +296,31 @@ int dreg_ngp_render_bwd(const float* origins, const float* viewdirs, const float
     if (n_rays == 0) return DREG_OK;
     if (!origins || !viewdirs || !jitter || !base16 || !color16 || !rgb || !grad_rgb || !grad_base || !grad_color || !workspace) return DREG_EINVAL;
     RenderBwdArgs a;
-    size_t slab_off, queue_off, total;
-    if (bwd_layout(n_rays, &a.chunk_rays, &a.n_chunks, &slab_off, &queue_off, &total) != DREG_OK || workspace_bytes < total) return DREG_EINVAL;
+    FbLayout w;
+    if (fb_layout(n_rays, BWD_LEAD, w) != DREG_OK || workspace_bytes < w.total) return DREG_EINVAL;
+    a.chunk_rays = w.chunk_items; a.n_chunks = w.n_chunks;
     char* ws = (char*)workspace;
     a.origins = origins; a.dirs = viewdirs; a.jitter = jitter; a.n_rays = n_rays;
-    const _Float16* b16 = (const _Float16*)base16;
-    const _Float16* c16 = (const _Float16*)color16;
-    if (march_fill_block(a, binary, rx, ry, rz, coarse_bits, b16 + 3072, b16, b16 + 2048, true, c16, c16 + 2048, c16 + 6144, offset, size, res, scale, hashed,
+    const NgpParams16 p = ngp_split_params(base16, color16);
+    if (march_fill_block(a, binary, rx, ry, rz, coarse_bits, p.table, p.w1, p.w2, true, p.cw1, p.cw2, p.cw3, offset, size, res, scale, hashed,
                          roi_aabb, scene_aabb, model_aabb, near_plane, far_plane, render_step_size, alpha_thre, true) != DREG_OK)
         return DREG_EINVAL;
     a.wf = (const float*)ws;
     a.eps = early_stop_eps;
     a.pass_bound = march_pass_bound(a.chunk_rays, (double)(a.n_max + 2));
     a.rgb = rgb; a.grad_rgb = grad_rgb;
-    a.grad_table = grad_base + 3072;
-    a.slabs = (float*)(ws + slab_off);
-    a.queue = (unsigned int*)(ws + queue_off);
-    if (hipMemsetAsync(ws + slab_off, 0, total - slab_off, (hipStream_t)stream) != hipSuccess) return DREG_ELAUNCH;
-    hipLaunchKernelGGL(ngp_bwd_weights_kernel, dim3(BWD_SLAB / 256), dim3(256), 0, (hipStream_t)stream, b16, c16, (float*)ws);
+    a.grad_table = grad_base + NGP_BASE_TABLE;
+    a.slabs = (float*)(ws + w.slab_off);
+    a.queue = (unsigned int*)(ws + w.queue_off);
+    if (hipMemsetAsync(ws + w.slab_off, 0, w.total - w.slab_off, (hipStream_t)stream) != hipSuccess) return DREG_ELAUNCH;
+    hipLaunchKernelGGL(ngp_bwd_weights_kernel, dim3(FB_SLAB / 256), dim3(256), 0, (hipStream_t)stream, (const _Float16*)base16, (const _Float16*)color16,
+                       (float*)ws);
     DREG_LAUNCH_CHECK();
     long waves = a.n_chunks;
     if (waves > g_render_bwd_waves) waves = g_render_bwd_waves;
     hipLaunchKernelGGL(ngp_render_bwd_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, a);
     DREG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ngp_bwd_reduce_kernel, dim3(BWD_SLAB / 256), dim3(256), 0, (hipStream_t)stream, (const float*)(ws + slab_off), a.n_chunks,
-                       grad_base, grad_color);
-    DREG_LAUNCH_CHECK();
-    return DREG_OK;
+    return fb_reduce(a.slabs, a.n_chunks, grad_base, grad_color, (hipStream_t)stream);
 }
 
 int dreg_ngp_adam_step(float* p, float* g, float* m, float* v, void* p16, size_t n, float lr, float beta1, float beta2, float eps, int step, void* stream)

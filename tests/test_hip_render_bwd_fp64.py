@@ -1,4 +1,4 @@
-"""GPU: the training backward of csrc/render_train.hip (ngp_render_bwd_kernel, ngp_bwd_reduce_kernel) against the fp64 restatement of
+"""GPU: the training backward of csrc/render_train.hip (ngp_render_bwd_kernel, fb_reduce_kernel) against the fp64 restatement of
 tests/render_bwd_restatement.py, element by element, on the flat planted field of tests/render_bwd_cases.py.
 
 On that field the encoding, both nets' activations and the colour are constants that fp32 and fp16 hold exactly, so the forward supplies
