@@ -66,6 +66,8 @@ struct Op {
     int fold_into = -1, res_from = -1;   // OP_BN (ReLU-free, large path) whose output only feeds BatchNorm `fold_into` as its residual: not applied, that layer applies it on the fly (res_from = this op)
     int bt = -1;                 // OP_BN on the one-launch small path: index of its record in the two BatchNorm tail tables
     size_t keep_var = 0, keep_sums = 0;   //   per-grid variances [B][C] / gradient sums [B][C][2] kept until the batched tail launch
+    int self_coef = 0;           // OP_BN on the large path without finalize launches (dreg_bn_self_coef_use): bit 0 forward (from epilogue chunk sums), bit 1 backward;
+                                 //   its tails join the batched launches through `bt`, keep_var / keep_sums then hold fp64 pairs [B][C][2]
 };
 struct HaloPack { const float* w; size_t off; int Cout, Cin, transposed, brick; };
 struct PackRec { const float* w; void* out; int Cout, Cin_real, inner, ntaps, for_dgrad, Kpad, dtype, row0; };
@@ -180,6 +182,7 @@ void dreg_exec_default_opts(dreg_exec_opts* o)
     std::memset(o, 0, sizeof(*o));
     o->sparse_grads = 1; o->bn_batch_tails = 1; o->fuse_stem = 1; o->sparse_stem = 1; o->fold_res_bn = 1; o->fold_splitk = 1;
     o->group_wgrad = 1; o->s2_accumulate = 1; o->fuse_bn_stats = 1; o->brick = 1; o->defer_head_pg = 0; o->pointwise_stream = 1;
+    o->bn_self_coef = 1;
 }
 void* dreg_exec_create(const int* tensors, int nt, const int* ops, int nops, const int64_t* params, int np)
 {
@@ -192,7 +195,7 @@ void* dreg_exec_create_opts(const int* tensors, int nt, const int* ops, int nops
     e->opt.brick &= 3;
     const int g_sparse_grads = e->opt.sparse_grads, g_bn_batch_tails = e->opt.bn_batch_tails, g_fuse_stem = e->opt.fuse_stem, g_sparse_stem = e->opt.sparse_stem,
               g_fold_res_bn = e->opt.fold_res_bn, g_fold_splitk = e->opt.fold_splitk, g_group_wgrad = e->opt.group_wgrad, g_fuse_bn_stats = e->opt.fuse_bn_stats,
-              g_brick = e->opt.brick;
+              g_brick = e->opt.brick, g_bn_self_coef = e->opt.bn_self_coef;
     e->t.resize(nt);
     for (int i = 0; i < nt; ++i) {
         Tensor& t = e->t[i];
@@ -320,6 +323,19 @@ void* dreg_exec_create_opts(const int* tensors, int nt, const int* ops, int nops
                 BnTailRec f{}, b{};
                 f.a = (const float*)o.aux1; f.b = (const float*)o.keep_var; f.o0 = e->prm[o.p2].val; f.o1 = e->prm[o.p3].val;
                 b.a = (const float*)o.keep_sums; b.b = nullptr; b.o0 = e->prm[o.w].grad; b.o1 = e->prm[o.b].grad;
+                f.B = b.B = x.B; f.V = b.V = (int)V; f.C = b.C = x.C; f.block0 = b.block0 = e->bn_blocks;
+                e->bn_blocks += (x.C + 255) / 256;
+                o.bt = (int)e->bn_fwd.size();
+                e->bn_fwd.push_back(f); e->bn_bwd.push_back(b);
+            } else if (g_bn_self_coef && g_bn_batch_tails && o.pool < 0 && !shared && o.fold_into < 0 &&
+                       (dreg_bn_self_coef_use(x.B, (int)V, x.C, 0, 0) || dreg_bn_self_coef_use(x.B, (int)V, x.C, 0, 1))) {
+                o.self_coef = (dreg_bn_self_coef_use(x.B, (int)V, x.C, 0, 0) ? 1 : 0) | (dreg_bn_self_coef_use(x.B, (int)V, x.C, 0, 1) ? 2 : 0);
+                const size_t kb = align256((size_t)x.B * x.C * 2 * sizeof(double));
+                o.keep_var = off; off += kb;
+                o.keep_sums = off; off += kb;
+                BnTailRec f{}, b{};       // a = nullptr: b names fp64 pairs
+                f.b = (const float*)o.keep_var; f.o0 = e->prm[o.p2].val; f.o1 = e->prm[o.p3].val;
+                b.b = (const float*)o.keep_sums; b.o0 = e->prm[o.w].grad; b.o1 = e->prm[o.b].grad;
                 f.B = b.B = x.B; f.V = b.V = (int)V; f.C = b.C = x.C; f.block0 = b.block0 = e->bn_blocks;
                 e->bn_blocks += (x.C + 255) / 256;
                 o.bt = (int)e->bn_fwd.size();
@@ -580,6 +596,7 @@ int dreg_exec_op_halo(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && o
 // dreg_exec_set_timing it is launched (and bracketed) alone, so its record names no row of a steady-state kernel trace
 int dreg_exec_op_wgrad_grouped(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].grp : 0; }
 // bit 0 / 1 / 2: the forward / plain data gradient / accumulating data gradient of op `op` runs on the streaming 1^3 kernel
+int dreg_exec_op_bn_self_coef(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].self_coef : 0; }
 int dreg_exec_op_pointwise(void* h, int op) { Exec* e = (Exec*)h; return op >= 0 && op < (int)e->ops.size() ? e->ops[op].pointwise : 0; }
 
 // 1 (default): weight / bias gradients on the executor's own second stream, overlapping the data-gradient chain; 0: one stream
@@ -642,8 +659,12 @@ static int upload_tables(Exec* e, char* A, hipStream_t st)
     e->reduce_abs = e->reduce;
     for (ReduceRec& r : e->reduce_abs) r.part = (const float*)(A + (size_t)r.part);
     std::vector<BnTailRec> f = e->bn_fwd, b = e->bn_bwd;
-    for (BnTailRec& r : f) { r.a = (const float*)(A + (size_t)r.a); r.b = (const float*)(A + (size_t)r.b); }
-    for (BnTailRec& r : b) r.a = (const float*)(A + (size_t)r.a);
+    for (size_t q = 0; q < f.size(); ++q) {
+        const bool self = e->bn_fwd[q].a == nullptr && e->bn_bwd[q].b != nullptr;     // a self-coefficient layer: a stays null, b = its fp64 pairs
+        f[q].b = (const float*)(A + (size_t)f[q].b);
+        if (self) b[q].b = (const float*)(A + (size_t)b[q].b);
+        else { f[q].a = (const float*)(A + (size_t)f[q].a); b[q].a = (const float*)(A + (size_t)b[q].a); }
+    }
     if (!e->reduce_abs.empty() && hipMemcpyAsync(A + e->off_rd, e->reduce_abs.data(), e->reduce_abs.size() * sizeof(ReduceRec), hipMemcpyHostToDevice, st) != hipSuccess) return DREG_ELAUNCH;
     if (!f.empty() && (hipMemcpyAsync(A + e->off_bnf, f.data(), f.size() * sizeof(BnTailRec), hipMemcpyHostToDevice, st) != hipSuccess ||
                        hipMemcpyAsync(A + e->off_bnb, b.data(), b.size() * sizeof(BnTailRec), hipMemcpyHostToDevice, st) != hipSuccess)) return DREG_ELAUNCH;
@@ -831,6 +852,12 @@ int dreg_exec_forward(void* h, void* arena, size_t arena_bytes, const void* pack
             void* out_p = o.fold_into >= 0 ? nullptr : act(o.out);       // folded branch: statistics, scale / shift only
             dreg_bn_extra ex{};
             if (o.res_from >= 0) { res_p = act(e->ops[o.res_from].in); ex.res_scale_shift = (const float*)(A + e->ops[o.res_from].aux0); }
+            if (train && sums_rpc[i] > 0 && (o.self_coef & 1) && out_p) {
+                CK(dreg_bn3d_fwd_self_coef(act(o.in), res_p, out_p, e->prm[o.w].val, e->prm[o.b].val, (float*)(A + o.aux0), (float*)(A + o.aux1),
+                                           (float*)(A + o.stats_off), sums_rpc[i], x.B, V, x.C, 1e-5f, o.relu, 0, (double*)(A + o.keep_var), ex.res_scale_shift, stream));
+                bn_done[o.bt] = 1;
+                continue;
+            }
             if (train && sums_rpc[i] > 0) {
                 CK(dreg_bn3d_fwd_ex(act(o.in), res_p, out_p, e->prm[o.w].val, e->prm[o.b].val, e->prm[o.p2].val, e->prm[o.p3].val,
                                     (float*)(A + o.aux0), (float*)(A + o.aux1), (float*)(A + o.stats_off), x.B, V, x.C, 1e-5f, 0.1f, 1, o.relu, 0,
@@ -841,7 +868,7 @@ int dreg_exec_forward(void* h, void* arena, size_t arena_bytes, const void* pack
             if (fwd_sk_bn == (int)i) { ex.splitk_part = (const float*)(A + e->off_ks); ex.splitk_nsplit = fwd_sk_n; ex.splitk_slice = fwd_sk_slice; fwd_sk_bn = -1; }
             CK(dreg_bn3d_fwd_ex(act(o.in), res_p, out_p, e->prm[o.w].val, e->prm[o.b].val, e->prm[o.p2].val, e->prm[o.p3].val,
                                 (float*)(A + o.aux0), (float*)(A + o.aux1), (float*)(A + e->off_bn_ws), x.B, V, x.C, 1e-5f, 0.1f, train, o.relu, 0,
-                                o.bt >= 0 ? (float*)(A + o.keep_var) : nullptr, &deferred, 0, &ex, stream));
+                                o.bt >= 0 && !o.self_coef ? (float*)(A + o.keep_var) : nullptr, &deferred, 0, &ex, stream));
             if (deferred) bn_done[o.bt] = 1;
         } else if (o.kind == OP_MAXPOOL) {
             CK(dreg_maxpool3d_fwd(act(o.in), act(o.out), (uint8_t*)(A + o.aux0), x.B, x.D, x.H, x.W, y.D, y.H, y.W, x.C, 0, stream));
@@ -1197,7 +1224,7 @@ int dreg_exec_backward_range(void* h, void* arena, size_t arena_bytes, const voi
                 // rare (never in ResNet-50/FPN): produce dres = masked gy through a second pass after dx has been folded in
                 CK(dreg_bn3d_bwd_defer_params(act(o.in), gy, act(o.out), (float*)(A + o.aux0), (float*)(A + o.aux1), dx, nullptr, e->prm[o.w].grad, e->prm[o.b].grad,
                                               (float*)(A + e->off_coef), (float*)(A + e->off_bn_ws), x.B, V, x.C, o.relu, 1, 0,
-                                              o.bt >= 0 ? (float*)(A + o.keep_sums) : nullptr, &deferred, stream));
+                                              o.bt >= 0 && !o.self_coef ? (float*)(A + o.keep_sums) : nullptr, &deferred, stream));
                 if (deferred) bn_done[o.bt] = 1;
                 CK(commit(o.in));
                 if (o.relu) CK(dreg_relu_bwd(act(o.out), gy, A + e->off_tmp, (size_t)x.B * V * x.C, 0, 0, 0, stream));
@@ -1205,11 +1232,19 @@ int dreg_exec_backward_range(void* h, void* arena, size_t arena_bytes, const voi
                 CK(commit(o.in2));
             } else {
                 // without a residual the ReLU mask is recomputed from x: y is not read
+                if ((o.self_coef & 2) && e->pend_sk_bn != i) {
+                    CK(dreg_bn3d_bwd_self_coef(act(o.in), gy, o.in2 >= 0 ? act(o.out) : nullptr, (float*)(A + o.aux0), (float*)(A + o.aux1), dx, dres,
+                                               (float*)(A + e->off_bn_ws), x.B, V, x.C, o.relu, 0, (double*)(A + o.keep_sums), stream));
+                    bn_done[o.bt] = 1;
+                    if (res_g && dres == (void*)(A + e->off_tmp)) { CK(commit(o.in2)); CK(commit(o.in)); }
+                    else { CK(commit(o.in)); if (res_g) CK(commit(o.in2)); }
+                    continue;
+                }
                 dreg_bn_extra ex{};
                 if (e->pend_sk_bn == i) { ex.splitk_part = (const float*)(A + e->off_ks); ex.splitk_nsplit = e->pend_sk_n; ex.splitk_slice = e->pend_sk_slice; e->pend_sk_bn = -1; }
                 CK(dreg_bn3d_bwd_ex(act(o.in), gy, o.in2 >= 0 ? act(o.out) : nullptr, (float*)(A + o.aux0), (float*)(A + o.aux1), dx, dres, e->prm[o.w].grad, e->prm[o.b].grad,
                                     (float*)(A + e->off_coef), (float*)(A + e->off_bn_ws), x.B, V, x.C, o.relu, 1, 0,
-                                    o.bt >= 0 ? (float*)(A + o.keep_sums) : nullptr, &deferred, &ex, stream));
+                                    o.bt >= 0 && !o.self_coef ? (float*)(A + o.keep_sums) : nullptr, &deferred, &ex, stream));
                 if (deferred) bn_done[o.bt] = 1;
                 if (res_g && dres == (void*)(A + e->off_tmp)) { CK(commit(o.in2)); CK(commit(o.in)); }
                 else { CK(commit(o.in)); if (res_g) CK(commit(o.in2)); }

@@ -154,6 +154,79 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(
     }
 }
 
+// The finalize arithmetic, stated once (bn_finalize_kernel / bn_bwd_finalize_kernel and the self-coefficient apply passes below).
+// Sums of one (grid b, channel c) over the chunk partials: lane k of 64 adds chunks k, k + 64, ... in fp64, then the xor butterfly
+// 32 -> 1 (wave_sum_d).  The butterfly is a fixed binary tree over the 64 lane sums — level o pairs k with k ^ o — so
+//   T(r, 64) = lane sum r,   T(r, S) = T(r, 2S) + T(r + S, 2S),   result = T(0, 1)
+// and any mapping that evaluates this tree gives the same bits (fp64 addition is commutative, the association is the tree's).
+__device__ __forceinline__ const float* bn_chunk_ptr(const float* __restrict__ partial, int b, int k, int c, int nchunks, int C)
+{
+    return partial + (((size_t)b * nchunks + k) * C + c) * 2;
+}
+// one wave per (b, c)
+__device__ __forceinline__ void bn_chunk_sums_wave(const float* __restrict__ partial, int b, int c, int nchunks, int C, int lane, double& s1, double& s2)
+{
+    s1 = 0.0; s2 = 0.0;
+#pragma unroll 8
+    for (int k = lane; k < nchunks; k += 64) {
+        const float2 p = *reinterpret_cast<const float2*>(bn_chunk_ptr(partial, b, k, c, nchunks, C));
+        s1 += p.x; s2 += p.y;
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+}
+// BNSC_P threads per (b, c): thread j forms the lane sums j, j + P, ... (a chunk past the end adds +0.0 to a sum that started at +0.0: the
+// same bits as not adding) and folds them through the tree levels 32 ... P: T(j, P).  bn_chunk_sums_join adds the levels below P.
+constexpr int BNSC_P = 4, BNSC_M = 64 / BNSC_P, BNSC_CH = 256 / BNSC_P;     // 256 threads: 64 channels per round, one thread j per wave
+static_assert(BNSC_P == 4, "bn_chunk_sums_join is written for four threads per channel");
+__device__ __forceinline__ void bn_chunk_sums_part(const float* __restrict__ partial, int b, int c, int nchunks, int C, int j, double& s1, double& s2)
+{
+    double a1[BNSC_M], a2[BNSC_M];
+#pragma unroll
+    for (int m = 0; m < BNSC_M; ++m) a1[m] = a2[m] = 0.0;
+    for (int k0 = 0; k0 < nchunks; k0 += 64) {
+#pragma unroll
+        for (int m = 0; m < BNSC_M; ++m) {
+            const int k = k0 + j + BNSC_P * m;
+            const bool ok = k < nchunks;
+            const float2 p = *reinterpret_cast<const float2*>(bn_chunk_ptr(partial, b, ok ? k : 0, c, nchunks, C));
+            a1[m] += ok ? (double)p.x : 0.0; a2[m] += ok ? (double)p.y : 0.0;
+        }
+    }
+#pragma unroll
+    for (int h = BNSC_M / 2; h > 0; h >>= 1)
+#pragma unroll
+        for (int m = 0; m < h; ++m) { a1[m] += a1[m + h]; a2[m] += a2[m + h]; }
+    s1 = a1[0]; s2 = a2[0];
+}
+__device__ __forceinline__ double bn_chunk_sums_join(double t0, double t1, double t2, double t3) { return (t0 + t2) + (t1 + t3); }   // levels 2 and 1
+
+struct BnFwdCoef { double mean, var; float scale, shift, rstd; };
+__device__ __forceinline__ BnFwdCoef bn_fwd_coef(double s1, double s2, int V, float ga, float be, float eps)
+{
+    BnFwdCoef k;
+    const double mean = s1 / V;
+    double var = s2 / V - mean * mean;
+    if (var < 0) var = 0;
+    const float rstd = 1.0f / sqrtf((float)var + eps);
+    k.mean = mean; k.var = var; k.rstd = rstd;
+    k.scale = ga * rstd;
+    k.shift = be - (float)mean * ga * rstd;
+    return k;
+}
+__device__ __forceinline__ void bn_fwd_coef_store(const BnFwdCoef& k, float* __restrict__ scale_shift, float* __restrict__ mean_rstd, size_t pc)
+{
+    scale_shift[pc] = k.scale; scale_shift[pc + 1] = k.shift;
+    mean_rstd[pc] = (float)k.mean; mean_rstd[pc + 1] = k.rstd;
+}
+// one grid's step of the running statistics (the grids are taken in order: one grid per BatchNorm call in the reference)
+__device__ __forceinline__ void bn_running_step(float& rm, float& rv, double mean, double var, int V, float momentum)
+{
+    const float unbiased = V > 1 ? (float)(var * V / (V - 1)) : (float)var;
+    rm = (1.f - momentum) * rm + momentum * (float)mean;
+    rv = (1.f - momentum) * rv + momentum * unbiased;
+}
+__device__ __forceinline__ void bn_bwd_coef(double s1, double s2, int V, float& c1, float& c2) { c1 = (float)(s1 / V); c2 = (float)(s2 / V); }
+
 // one block per channel, one wave per grid: finalise mean / biased var (lanes stride over the chunk partials, all loads of a
 // wave in flight at once), emit scale/shift and (mean, rstd); thread 0 then updates the running stats sequentially over the grids
 // (reference: one grid per BatchNorm call, src then tgt — nerf_regtr.py:135).
@@ -177,34 +250,18 @@ __global__ __launch_bounds__(512) void bn_finalize_kernel(const float* __restric
     }
     __shared__ double stat[BN_MAX_GRIDS][2];
     for (int b = wave; b < B; b += nw) {
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll 8
-        for (int k = lane; k < nchunks; k += 64) {
-            const float2 p = *reinterpret_cast<const float2*>(partial + (((size_t)b * nchunks + k) * C + c) * 2);
-            s1 += p.x; s2 += p.y;
-        }
-        s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-        const double mean = s1 / V;
-        double var = s2 / V - mean * mean;
-        if (var < 0) var = 0;
+        double s1, s2;
+        bn_chunk_sums_wave(partial, b, c, nchunks, C, lane, s1, s2);
+        const BnFwdCoef k = bn_fwd_coef(s1, s2, V, ga, be, eps);
         if (lane == 0) {
-            const float rstd = 1.0f / sqrtf((float)var + eps);
-            scale_shift[((size_t)b * C + c) * 2] = ga * rstd;
-            scale_shift[((size_t)b * C + c) * 2 + 1] = be - (float)mean * ga * rstd;
-            mean_rstd[((size_t)b * C + c) * 2] = (float)mean;
-            mean_rstd[((size_t)b * C + c) * 2 + 1] = rstd;
-            stat[b][0] = mean; stat[b][1] = var;
+            bn_fwd_coef_store(k, scale_shift, mean_rstd, ((size_t)b * C + c) * 2);
+            stat[b][0] = k.mean; stat[b][1] = k.var;
         }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         float rm = running_mean[c], rv = running_var[c];
-        for (int b = 0; b < B; ++b) {
-            const double mean = stat[b][0], var = stat[b][1];
-            const float unbiased = V > 1 ? (float)(var * V / (V - 1)) : (float)var;
-            rm = (1.f - momentum) * rm + momentum * (float)mean;
-            rv = (1.f - momentum) * rv + momentum * unbiased;
-        }
+        for (int b = 0; b < B; ++b) bn_running_step(rm, rv, stat[b][0], stat[b][1], V, momentum);
         running_mean[c] = rm; running_var[c] = rv;
     }
 }
@@ -241,16 +298,10 @@ __global__ __launch_bounds__(512) void bn_bwd_finalize_kernel(const float* __res
     const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     __shared__ double stat[BN_MAX_GRIDS][2];
     for (int b = wave; b < B; b += nw) {
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll 8
-        for (int k = lane; k < nchunks; k += 64) {
-            const float2 p = *reinterpret_cast<const float2*>(partial + (((size_t)b * nchunks + k) * C + c) * 2);
-            s1 += p.x; s2 += p.y;
-        }
-        s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+        double s1, s2;
+        bn_chunk_sums_wave(partial, b, c, nchunks, C, lane, s1, s2);
         if (lane == 0) {
-            coef[((size_t)b * C + c) * 2] = (float)(s1 / V);
-            coef[((size_t)b * C + c) * 2 + 1] = (float)(s2 / V);
+            bn_bwd_coef(s1, s2, V, coef[((size_t)b * C + c) * 2], coef[((size_t)b * C + c) * 2 + 1]);
             stat[b][0] = s1; stat[b][1] = s2;
         }
     }
@@ -301,22 +352,13 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict
 // res_ss (optional): the residual is itself the output of a ReLU-free BatchNorm that was not applied (the downsample branch of a
 // bottleneck's first block, resnet3d.py:104-110): res holds that layer's INPUT and res_ss its (scale, shift); its output is formed here,
 // rounded to the activation dtype exactly as the separate apply pass stored it (bit-identical, one 2 x tensor pass less).
+// the row walk of the column-fixed forward apply pass: one channel granule per thread, its parameters in registers
 template <typename T, int UN>
-__global__ __launch_bounds__(256) void bn_apply_cols_kernel(const T* __restrict__ x, const float* __restrict__ scale_shift, const T* __restrict__ res,
-                                                            T* __restrict__ y, int V, int C, int rows_per_chunk, int relu,
-                                                            const float* __restrict__ res_ss = nullptr)
+__device__ __forceinline__ void bn_apply_cols_walk(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, int b, int cg, int r0, int rpi,
+                                                   int v0, int v1, int V, int C, int relu, bool res_ss,
+                                                   const float (&sc)[Gran<T>::G], const float (&sh)[Gran<T>::G], const float (&rsc)[Gran<T>::G], const float (&rsh)[Gran<T>::G])
 {
     constexpr int G = Gran<T>::G;
-    const int CG = C / G, cgs = CG < 256 ? CG : 256, rpi = 256 / cgs;
-    const int t = threadIdx.x, cg = blockIdx.z * cgs + (t % cgs), r0 = t / cgs, b = blockIdx.y;
-    if (r0 >= rpi || cg >= CG) return;
-    const int v0 = blockIdx.x * rows_per_chunk, v1 = min(v0 + rows_per_chunk, V);
-    float sc[G], sh[G], rsc[G], rsh[G];
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-        sc[i] = scale_shift[((size_t)b * C + cg * G + i) * 2]; sh[i] = scale_shift[((size_t)b * C + cg * G + i) * 2 + 1];
-        if (res_ss) { rsc[i] = res_ss[((size_t)b * C + cg * G + i) * 2]; rsh[i] = res_ss[((size_t)b * C + cg * G + i) * 2 + 1]; }
-    }
     for (int v = v0 + r0; v < v1; v += rpi * UN) {
         float xv[UN][G], rv[UN][G];
 #pragma unroll
@@ -344,23 +386,30 @@ __global__ __launch_bounds__(256) void bn_apply_cols_kernel(const T* __restrict_
     }
 }
 template <typename T, int UN>
-__global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restrict__ x, const T* dy, const T* __restrict__ y,
-                                                                const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift,
-                                                                const float* __restrict__ coef, T* __restrict__ dx, T* dres,
-                                                                int V, int C, int rows_per_chunk, int relu, int g_stored = 0)
+__global__ __launch_bounds__(256) void bn_apply_cols_kernel(const T* __restrict__ x, const float* __restrict__ scale_shift, const T* __restrict__ res,
+                                                            T* __restrict__ y, int V, int C, int rows_per_chunk, int relu,
+                                                            const float* __restrict__ res_ss = nullptr)
 {
     constexpr int G = Gran<T>::G;
     const int CG = C / G, cgs = CG < 256 ? CG : 256, rpi = 256 / cgs;
     const int t = threadIdx.x, cg = blockIdx.z * cgs + (t % cgs), r0 = t / cgs, b = blockIdx.y;
     if (r0 >= rpi || cg >= CG) return;
-    if (g_stored) { dy = dres; dres = nullptr; relu = 0; }     // the statistics pass stored the masked gradient in dres: one tensor read less
     const int v0 = blockIdx.x * rows_per_chunk, v1 = min(v0 + rows_per_chunk, V);
-    float mu[G], rs[G], sc[G], sh[G], c1[G], c2[G];
+    float sc[G], sh[G], rsc[G], rsh[G];
 #pragma unroll
     for (int i = 0; i < G; ++i) {
-        const size_t pc = ((size_t)b * C + cg * G + i) * 2;
-        mu[i] = mean_rstd[pc]; rs[i] = mean_rstd[pc + 1]; sc[i] = scale_shift[pc]; sh[i] = scale_shift[pc + 1]; c1[i] = coef[pc]; c2[i] = coef[pc + 1];
+        sc[i] = scale_shift[((size_t)b * C + cg * G + i) * 2]; sh[i] = scale_shift[((size_t)b * C + cg * G + i) * 2 + 1];
+        if (res_ss) { rsc[i] = res_ss[((size_t)b * C + cg * G + i) * 2]; rsh[i] = res_ss[((size_t)b * C + cg * G + i) * 2 + 1]; }
     }
+    bn_apply_cols_walk<T, UN>(x, res, y, b, cg, r0, rpi, v0, v1, V, C, relu, res_ss != nullptr, sc, sh, rsc, rsh);
+}
+template <typename T, int UN>
+__device__ __forceinline__ void bn_bwd_apply_cols_walk(const T* __restrict__ x, const T* dy, const T* __restrict__ y, T* __restrict__ dx, T* dres, int b, int cg, int r0, int rpi,
+                                                       int v0, int v1, int V, int C, int relu,
+                                                       const float (&mu)[Gran<T>::G], const float (&rs)[Gran<T>::G], const float (&sc)[Gran<T>::G], const float (&sh)[Gran<T>::G],
+                                                       const float (&c1)[Gran<T>::G], const float (&c2)[Gran<T>::G])
+{
+    constexpr int G = Gran<T>::G;
     const bool remask = relu && y == nullptr;
     for (int v = v0 + r0; v < v1; v += rpi * UN) {
         float xv[UN][G], gv[UN][G], yv[UN][G];
@@ -392,6 +441,116 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restr
                 Gran<T>::st(dx + off, xv[u]);
             }
     }
+}
+template <typename T, int UN>
+__global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restrict__ x, const T* dy, const T* __restrict__ y,
+                                                                const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift,
+                                                                const float* __restrict__ coef, T* __restrict__ dx, T* dres,
+                                                                int V, int C, int rows_per_chunk, int relu, int g_stored = 0)
+{
+    constexpr int G = Gran<T>::G;
+    const int CG = C / G, cgs = CG < 256 ? CG : 256, rpi = 256 / cgs;
+    const int t = threadIdx.x, cg = blockIdx.z * cgs + (t % cgs), r0 = t / cgs, b = blockIdx.y;
+    if (r0 >= rpi || cg >= CG) return;
+    if (g_stored) { dy = dres; dres = nullptr; relu = 0; }     // the statistics pass stored the masked gradient in dres: one tensor read less
+    const int v0 = blockIdx.x * rows_per_chunk, v1 = min(v0 + rows_per_chunk, V);
+    float mu[G], rs[G], sc[G], sh[G], c1[G], c2[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const size_t pc = ((size_t)b * C + cg * G + i) * 2;
+        mu[i] = mean_rstd[pc]; rs[i] = mean_rstd[pc + 1]; sc[i] = scale_shift[pc]; sh[i] = scale_shift[pc + 1]; c1[i] = coef[pc]; c2[i] = coef[pc + 1];
+    }
+    bn_bwd_apply_cols_walk<T, UN>(x, dy, y, dx, dres, b, cg, r0, rpi, v0, v1, V, C, relu, mu, rs, sc, sh, c1, c2);
+}
+
+// Self-coefficient forms of the two column-fixed apply passes: no finalize launch in front of them.  Every workgroup first forms the
+// coefficients of ITS channels of grid b from the chunk sums (L2-resident; bn_chunk_sums_part / _join: the finalize kernels' bits) and
+// leaves them in LDS, then walks its rows as above.  A workgroup covers at most BNSC_MAXC channels (wider layers: blockIdx.z), and its
+// rows (rows_per_wg) are independent of the statistics chunking (nchunks sums per (b, c)).  The workgroups of blockIdx.x == 0 also
+// write what the finalize kernels wrote per (b, c): scale_shift / mean_rstd (forward), and the fp64 pairs the cross-grid tail needs in
+// keep [B][C][2]: (mean, var) forward, (sum g, sum g xhat) backward (bn_tail_batched_kernel, records with a == nullptr).  No
+// cross-workgroup communication.
+constexpr int BNSC_MAXC = 128;
+// PASS 0: out0 / out1 = scale / shift;  PASS 1: c1 / c2.  s_out: [2][BNSC_MAXC] floats, red: [BNSC_P][BNSC_CH][2] doubles.
+template <int PASS>
+__device__ __forceinline__ void bn_self_prologue(const float* __restrict__ sums, int b, int c_lo, int nc, int nchunks, int C, int V,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                 float* __restrict__ scale_shift, float* __restrict__ mean_rstd, double* __restrict__ keep, bool writer,
+                                                 float (*s_out)[BNSC_MAXC], double (*red)[BNSC_CH][2])
+{
+    const int ci = threadIdx.x % BNSC_CH, j = threadIdx.x / BNSC_CH;
+    for (int cr = 0; cr < nc; cr += BNSC_CH) {
+        const bool valid = cr + ci < nc;
+        const int c = c_lo + cr + ci;
+        double s1 = 0.0, s2 = 0.0;
+        if (valid) {
+            bn_chunk_sums_part(sums, b, c, nchunks, C, j, s1, s2);
+            red[j][ci][0] = s1; red[j][ci][1] = s2;
+        }
+        __syncthreads();
+        if (valid && j == 0) {
+            s1 = bn_chunk_sums_join(s1, red[1][ci][0], red[2][ci][0], red[3][ci][0]);
+            s2 = bn_chunk_sums_join(s2, red[1][ci][1], red[2][ci][1], red[3][ci][1]);
+            const size_t pc = ((size_t)b * C + c) * 2;
+            if (PASS == 0) {
+                const BnFwdCoef k = bn_fwd_coef(s1, s2, V, gamma[c], beta[c], eps);
+                s_out[0][cr + ci] = k.scale; s_out[1][cr + ci] = k.shift;
+                if (writer) { bn_fwd_coef_store(k, scale_shift, mean_rstd, pc); keep[pc] = k.mean; keep[pc + 1] = k.var; }
+            } else {
+                bn_bwd_coef(s1, s2, V, s_out[0][cr + ci], s_out[1][cr + ci]);
+                if (writer) { keep[pc] = s1; keep[pc + 1] = s2; }
+            }
+        }
+        __syncthreads();
+    }
+}
+template <typename T, int UN>
+__global__ __launch_bounds__(256) void bn_apply_self_kernel(const T* __restrict__ x, const float* __restrict__ sums, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const T* __restrict__ res, T* __restrict__ y,
+                                                            float* __restrict__ scale_shift, float* __restrict__ mean_rstd, double* __restrict__ keep,
+                                                            int V, int C, int nchunks, int rows_per_wg, float eps, int relu, const float* __restrict__ res_ss)
+{
+    constexpr int G = Gran<T>::G, CGS = BNSC_MAXC / G;
+    const int CG = C / G, cgs = CG < CGS ? CG : CGS, rpi = 256 / cgs;
+    const int t = threadIdx.x, lg = t % cgs, cg = blockIdx.z * cgs + lg, r0 = t / cgs, b = blockIdx.y;
+    __shared__ float s_out[2][BNSC_MAXC];
+    __shared__ double red[BNSC_P][BNSC_CH][2];
+    const int c_lo = blockIdx.z * cgs * G;
+    bn_self_prologue<0>(sums, b, c_lo, min(cgs * G, C - c_lo), nchunks, C, V, gamma, beta, eps, scale_shift, mean_rstd, keep, blockIdx.x == 0, s_out, red);
+    if (r0 >= rpi || cg >= CG) return;
+    const int v0 = blockIdx.x * rows_per_wg, v1 = min(v0 + rows_per_wg, V);
+    float sc[G], sh[G], rsc[G], rsh[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        sc[i] = s_out[0][lg * G + i]; sh[i] = s_out[1][lg * G + i];
+        if (res_ss) { rsc[i] = res_ss[((size_t)b * C + cg * G + i) * 2]; rsh[i] = res_ss[((size_t)b * C + cg * G + i) * 2 + 1]; }
+    }
+    bn_apply_cols_walk<T, UN>(x, res, y, b, cg, r0, rpi, v0, v1, V, C, relu, res_ss != nullptr, sc, sh, rsc, rsh);
+}
+template <typename T, int UN>
+__global__ __launch_bounds__(256) void bn_bwd_apply_self_kernel(const T* __restrict__ x, const T* dy, const T* __restrict__ y, const float* __restrict__ sums,
+                                                                const float* __restrict__ mean_rstd, const float* __restrict__ scale_shift,
+                                                                T* __restrict__ dx, T* dres, double* __restrict__ keep,
+                                                                int V, int C, int nchunks, int rows_per_wg, int relu, int g_stored)
+{
+    constexpr int G = Gran<T>::G, CGS = BNSC_MAXC / G;
+    const int CG = C / G, cgs = CG < CGS ? CG : CGS, rpi = 256 / cgs;
+    const int t = threadIdx.x, lg = t % cgs, cg = blockIdx.z * cgs + lg, r0 = t / cgs, b = blockIdx.y;
+    __shared__ float s_out[2][BNSC_MAXC];
+    __shared__ double red[BNSC_P][BNSC_CH][2];
+    const int c_lo = blockIdx.z * cgs * G;
+    bn_self_prologue<1>(sums, b, c_lo, min(cgs * G, C - c_lo), nchunks, C, V, nullptr, nullptr, 0.f, nullptr, nullptr, keep, blockIdx.x == 0, s_out, red);
+    if (r0 >= rpi || cg >= CG) return;
+    if (g_stored) { dy = dres; dres = nullptr; relu = 0; }     // as bn_bwd_apply_cols_kernel
+    const int v0 = blockIdx.x * rows_per_wg, v1 = min(v0 + rows_per_wg, V);
+    float mu[G], rs[G], sc[G], sh[G], c1[G], c2[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const size_t pc = ((size_t)b * C + cg * G + i) * 2;
+        mu[i] = mean_rstd[pc]; rs[i] = mean_rstd[pc + 1]; sc[i] = scale_shift[pc]; sh[i] = scale_shift[pc + 1];
+        c1[i] = s_out[0][lg * G + i]; c2[i] = s_out[1][lg * G + i];
+    }
+    bn_bwd_apply_cols_walk<T, UN>(x, dy, y, dx, dres, b, cg, r0, rpi, v0, v1, V, C, relu, mu, rs, sc, sh, c1, c2);
 }
 
 // ------------------------------------------------------------------------------------------------ small volumes: fused passes
@@ -684,6 +843,7 @@ __global__ void bn_param_grad_kernel(const float* __restrict__ sums, float* __re
 struct BnTailDesc {              // 48 bytes
     const float* a;              // running update: mean_rstd [B][C][2];   parameter gradients: sums [B][C][2]
     const float* b;              // running update: var [B][C];            parameter gradients: unused
+                                 // a == nullptr (a self-coefficient layer of the large path): b = fp64 pairs [B][C][2]: (mean, var) / (sum g, sum g xhat)
     float* o0; float* o1;        // running update: running_mean / running_var;   parameter gradients: dgamma / dbeta
     int B, V, C, block0;         // block0: first workgroup (256 channels each) of this layer in the batched launch
 };
@@ -700,6 +860,20 @@ __global__ void bn_tail_batched_kernel(const BnTailDesc* __restrict__ descs, int
     const BnTailDesc d = descs[lo];
     const int c = (blk - d.block0) * blockDim.x + threadIdx.x;
     if (c >= d.C) return;
+    if (d.a == nullptr) {       // a self-coefficient layer: b = fp64 pairs [B][C][2]; bn_finalize_kernel's / bn_bwd_finalize_kernel's thread-0 tail
+        const double* p = reinterpret_cast<const double*>(d.b);
+        if (WHAT == 0) {
+            float rm = d.o0[c], rv = d.o1[c];
+            for (int b = 0; b < d.B; ++b) bn_running_step(rm, rv, p[((size_t)b * d.C + c) * 2], p[((size_t)b * d.C + c) * 2 + 1], d.V, momentum);
+            d.o0[c] = rm; d.o1[c] = rv;
+        } else {
+            double dg = 0.0, db = 0.0;
+            for (int b = 0; b < d.B; ++b) { db += p[((size_t)b * d.C + c) * 2]; dg += p[((size_t)b * d.C + c) * 2 + 1]; }
+            d.o0[c] = accumulate ? d.o0[c] + (float)dg : (float)dg;
+            d.o1[c] = accumulate ? d.o1[c] + (float)db : (float)db;
+        }
+        return;
+    }
     if (WHAT == 0) {
         float rm = d.o0[c], rv = d.o1[c];
         for (int b = 0; b < d.B; ++b) {
@@ -1922,6 +2096,17 @@ static inline int nblocks(size_t total, int per = 256, int cap = 8192) {
 // apply kernels do test): a last slab that is not full would read and write past the row.  No layer has such a channel count (more than 256
 // granules, not a multiple of 256: fp32 C = 1536); the entry points that launch those kernels refuse it.
 static inline bool slabs_ragged(int CG) { return CG > 256 && CG % 256 != 0; }
+// self-coefficient apply passes: channel slabs of one workgroup, and its rows — the statistics chunk, doubled while the launch would have more
+// workgroups than g_bn_self_wgs (512: profiles/bn_selfcoef_by_shape.txt) (every workgroup repeats the prologue of its channels: fewer, longer workgroups amortise it)
+DREG_KNOB(int, g_bn_self_wgs, 512);      // tuning (include/dreg_nerf_probe.h)
+static inline int bn_rows_per_chunk(int V);
+static inline int bn_self_slabs(int C, int G) { const int CG = C / G, cgs = CG < BNSC_MAXC / G ? CG : BNSC_MAXC / G; return (CG + cgs - 1) / cgs; }
+static inline int bn_self_rows(int B, int V, int C, int G)
+{
+    int rows = bn_rows_per_chunk(V);
+    while (rows < V && (long long)((V + rows - 1) / rows) * B * bn_self_slabs(C, G) > g_bn_self_wgs) rows *= 2;
+    return rows;
+}
 static inline int bn_rows_per_chunk(int V) { return V >= 262144 ? 512 : V >= 32768 ? 256 : V >= 4096 ? 128 : V >= 512 ? 32 : (V >= 8 ? 8 : V); }
 
 extern "C" {
@@ -1931,6 +2116,7 @@ void dreg_bn_set_debug_skip(int mask) { g_bn_debug_skip = mask; }
 void dreg_bn_set_store_g(int enable) { g_bn_store_g = enable ? 1 : 0; }
 void dreg_bn_set_small_regs(int enable) { g_bn_small_regs = enable ? 1 : 0; }
 void dreg_bn_set_small_max_voxels(int v) { g_bn_small_maxv = v; }
+void dreg_bn_set_self_wgs(int n) { g_bn_self_wgs = n > 0 ? n : 512; }
 #endif
 int dreg_bn_num_chunks(int V) { const int r = bn_rows_per_chunk(V); return (V + r - 1) / r; }
 
@@ -1939,7 +2125,7 @@ int dreg_bn_num_chunks(int V) { const int r = bn_rows_per_chunk(V); return (V + 
 static int bn3d_fwd_impl(const void* x, const void* res, void* y, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, float* scale_shift, float* mean_rstd, float* workspace,
                          int B, int V, int C, float eps, float momentum, int train, int relu, int dtype, void* stream, float* var_keep, int* deferred,
-                         int sums_rows_per_chunk = 0, const dreg_bn_extra* ex = nullptr);
+                         int sums_rows_per_chunk = 0, const dreg_bn_extra* ex = nullptr, double* self_keep = nullptr);
 int dreg_bn3d_fwd(const void* x, const void* res, void* y, const float* gamma, const float* beta,
                   float* running_mean, float* running_var, float* scale_shift, float* mean_rstd, float* workspace,
                   int B, int V, int C, float eps, float momentum, int train, int relu, int dtype, void* stream)
@@ -1977,22 +2163,37 @@ int dreg_bn3d_fwd_ex(const void* x, const void* res, void* y, const float* gamma
                          sums_rows_per_chunk > 0 ? 1 : train, relu, dtype, stream, var_keep, deferred, sums_rows_per_chunk, ex);
 }
 int dreg_bn_small(int B, int V, int C, int dtype) { return bn_small_ok(B, V, C, dtype == 0 ? 8 : 4) ? 1 : 0; }
-// descs_dev: n records of 48 bytes { const float* mean_rstd; const float* var; float* running_mean; float* running_var; int B, V, C, block0; }
-// with block0 = sum of ceil(C / 256) of the records before; workgroups [block_base, block_base + nblocks) run.
-int dreg_bn_running_update_batched(const void* descs_dev, int n, int block_base, int nblocks, float momentum, void* stream)
+// Self-coefficient forms (bn_apply_self_kernel / bn_bwd_apply_self_kernel).  _supported: the launch can run (training mode, large path).
+// _use: ... and it is the faster form (tools/bench_bn_selfcoef.py, profiles/bn_selfcoef_by_shape.txt); read by the trunk executor.
+int dreg_bn_self_coef_supported(int B, int V, int C, int dtype)
 {
-    if (n <= 0 || nblocks <= 0) return DREG_OK;
-    hipLaunchKernelGGL(bn_tail_batched_kernel<0>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const BnTailDesc*)descs_dev, n, block_base, momentum, 0);
-    DREG_LAUNCH_CHECK();
-    return DREG_OK;
+    const int G = dtype == 0 ? 8 : 4;
+    return (B >= 1 && B <= BN_MAX_GRIDS && V >= 2 && C >= G && C % G == 0 && !slabs_ragged(C / G) && !bn_small_ok(B, V, C, G)) ? 1 : 0;
 }
-// the same table layout with { const float* sums; unused; float* dgamma; float* dbeta; ... }
-int dreg_bn_param_grad_batched(const void* descs_dev, int n, int block_base, int nblocks, int accumulate, void* stream)
+int dreg_bn_self_coef_use(int B, int V, int C, int dtype, int backward)
 {
-    if (n <= 0 || nblocks <= 0) return DREG_OK;
-    hipLaunchKernelGGL(bn_tail_batched_kernel<1>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const BnTailDesc*)descs_dev, n, block_base, 0.f, accumulate);
-    DREG_LAUNCH_CHECK();
-    return DREG_OK;
+    // Measured shapes only (bf16, profiles/bn_selfcoef_by_shape.txt); everything else keeps its finalize launch.  The prologue costs
+    // chunks x channels x 8 bytes of L2 reads per workgroup: at 16^3 (32 chunks) the fused launch wins in every width and both directions;
+    // at 32^3 (128 chunks, 256 from the convolution epilogues) only the backward passes of 64 and 256 channels do.
+    if (!dreg_bn_self_coef_supported(B, V, C, dtype) || dtype != 0 || B < 2 || B > 16) return 0;
+    if (V == 4096) return (C == 128 || C == 256 || C == 512) ? 1 : 0;
+    if (V == 32768) return (backward && (C == 64 || C == 256)) ? 1 : 0;
+    return 0;
+}
+int dreg_bn_self_coef_rows(int B, int V, int C, int dtype) { return bn_self_rows(B, V, C, dtype == 0 ? 8 : 4); }
+// Training-mode forward from chunk sums (dreg_bn3d_fwd_from_sums) without the finalize launch: scale_shift / mean_rstd are written by the
+// apply pass, the per-grid (mean, var) go to keep [B][C][2] (fp64) and the running statistics are left to dreg_bn_running_update_batched
+// (record: a = NULL, b = keep).  res_scale_shift as dreg_bn_extra's (may be NULL).  DREG_EINVAL where dreg_bn_self_coef_supported says 0.
+int dreg_bn3d_fwd_self_coef(const void* x, const void* res, void* y, const float* gamma, const float* beta, float* scale_shift, float* mean_rstd,
+                            float* sums, int rows_per_chunk, int B, int V, int C, float eps, int relu, int dtype, double* keep,
+                            const float* res_scale_shift, void* stream)
+{
+    if (rows_per_chunk <= 0 || !keep) return DREG_EINVAL;
+    dreg_bn_extra ex{};
+    ex.res_scale_shift = res_scale_shift;
+    int deferred = 0;
+    return bn3d_fwd_impl(x, res, y, gamma, beta, nullptr, nullptr, scale_shift, mean_rstd, sums, B, V, C, eps, 0.f, 1, relu, dtype, stream, nullptr, &deferred,
+                         rows_per_chunk, &ex, keep);
 }
 // The next large-path forward call's residual is the INPUT of a ReLU-free BatchNorm whose (scale, shift) are res_scale_shift (that layer was
 // run with y == nullptr: statistics + finalize only); consumed by that one call.  See bn_apply_cols_kernel.
@@ -2007,7 +2208,7 @@ int dreg_bn_small_in_regs(int B, int V, int C, int dtype)
 static int bn3d_fwd_impl(const void* x, const void* res, void* y, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, float* scale_shift, float* mean_rstd, float* workspace,
                          int B, int V, int C, float eps, float momentum, int train, int relu, int dtype, void* stream, float* var_keep, int* deferred,
-                         int sums_rows_per_chunk, const dreg_bn_extra* ex)
+                         int sums_rows_per_chunk, const dreg_bn_extra* ex, double* self_keep)
 {
     hipStream_t st = (hipStream_t)stream;
     const float* res_ss = ex ? ex->res_scale_shift : nullptr;
@@ -2040,6 +2241,18 @@ static int bn3d_fwd_impl(const void* x, const void* res, void* y, const float* g
         return DREG_OK;
     }
     if (train && V < 2) return DREG_EINVAL;      // torch raises for one value per channel
+    if (self_keep) {      // self-coefficient form: no finalize launch; the caller runs the batched tail over self_keep (*deferred = 1)
+        if (!presummed || !y || !deferred || !dreg_bn_self_coef_supported(B, V, C, dtype)) return DREG_EINVAL;
+        const int rows = bn_self_rows(B, V, C, G);
+        const dim3 sgrid((V + rows - 1) / rows, B, bn_self_slabs(C, G));
+        if (dtype == 0) hipLaunchKernelGGL((bn_apply_self_kernel<bf16_t, 4>), sgrid, dim3(256), 0, st, (const bf16_t*)x, workspace, gamma, beta, (const bf16_t*)res, (bf16_t*)y, scale_shift, mean_rstd, self_keep,
+                                           V, C, V / sums_rows_per_chunk, rows, eps, relu, res ? res_ss : nullptr);
+        else hipLaunchKernelGGL((bn_apply_self_kernel<float, 4>), sgrid, dim3(256), 0, st, (const float*)x, workspace, gamma, beta, (const float*)res, (float*)y, scale_shift, mean_rstd, self_keep,
+                                V, C, V / sums_rows_per_chunk, rows, eps, relu, res ? res_ss : nullptr);
+        DREG_LAUNCH_CHECK();
+        *deferred = 1;
+        return DREG_OK;
+    }
     if (B > BN_MAX_GRIDS || (train && !presummed && slabs_ragged(CG))) return DREG_EINVAL;      // refused before anything is launched
     if (train && !presummed && !(g_bn_debug_skip & 1)) {
         dim3 grid(nch, B, slabs);
@@ -2063,7 +2276,7 @@ static int bn3d_fwd_impl(const void* x, const void* res, void* y, const float* g
 // read less in both passes.
 static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const float* scale_shift, const float* mean_rstd,
                          void* dx, void* dres, float* dgamma, float* dbeta, float* coef, float* workspace,
-                         int B, int V, int C, int relu, int accumulate, int dtype, void* stream, float* sums_keep, int* deferred, const dreg_bn_extra* ex = nullptr);
+                         int B, int V, int C, int relu, int accumulate, int dtype, void* stream, float* sums_keep, int* deferred, const dreg_bn_extra* ex = nullptr, double* self_keep = nullptr);
 int dreg_bn3d_bwd(const void* x, const void* dy, const void* y, const float* scale_shift, const float* mean_rstd,
                   void* dx, void* dres, float* dgamma, float* dbeta, float* coef, float* workspace,
                   int B, int V, int C, int relu, int accumulate, int dtype, void* stream)
@@ -2085,9 +2298,35 @@ int dreg_bn3d_bwd_ex(const void* x, const void* dy, const void* y, const float* 
 {
     return bn3d_bwd_impl(x, dy, y, scale_shift, mean_rstd, dx, dres, dgamma, dbeta, coef, workspace, B, V, C, relu, accumulate, dtype, stream, sums_keep, deferred, ex);
 }
+// Backward (dreg_bn3d_bwd) without the finalize launch: the per-grid (sum g, sum g xhat) go to keep [B][C][2] (fp64); dgamma / dbeta are
+// left to dreg_bn_param_grad_batched (record: a = NULL, b = keep).
+int dreg_bn3d_bwd_self_coef(const void* x, const void* dy, const void* y, const float* scale_shift, const float* mean_rstd,
+                            void* dx, void* dres, float* workspace, int B, int V, int C, int relu, int dtype, double* keep, void* stream)
+{
+    if (!keep) return DREG_EINVAL;
+    int deferred = 0;
+    return bn3d_bwd_impl(x, dy, y, scale_shift, mean_rstd, dx, dres, nullptr, nullptr, nullptr, workspace, B, V, C, relu, 0, dtype, stream, nullptr, &deferred, nullptr, keep);
+}
+// descs_dev: n records of 48 bytes { const float* mean_rstd; const float* var; float* running_mean; float* running_var; int B, V, C, block0; }
+// with block0 = sum of ceil(C / 256) of the records before; workgroups [block_base, block_base + nblocks) run.
+int dreg_bn_running_update_batched(const void* descs_dev, int n, int block_base, int nblocks, float momentum, void* stream)
+{
+    if (n <= 0 || nblocks <= 0) return DREG_OK;
+    hipLaunchKernelGGL(bn_tail_batched_kernel<0>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const BnTailDesc*)descs_dev, n, block_base, momentum, 0);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
+// the same table layout with { const float* sums; unused; float* dgamma; float* dbeta; ... }
+int dreg_bn_param_grad_batched(const void* descs_dev, int n, int block_base, int nblocks, int accumulate, void* stream)
+{
+    if (n <= 0 || nblocks <= 0) return DREG_OK;
+    hipLaunchKernelGGL(bn_tail_batched_kernel<1>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const BnTailDesc*)descs_dev, n, block_base, 0.f, accumulate);
+    DREG_LAUNCH_CHECK();
+    return DREG_OK;
+}
 static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const float* scale_shift, const float* mean_rstd,
                          void* dx, void* dres, float* dgamma, float* dbeta, float* coef, float* workspace,
-                         int B, int V, int C, int relu, int accumulate, int dtype, void* stream, float* sums_keep, int* deferred, const dreg_bn_extra* ex)
+                         int B, int V, int C, int relu, int accumulate, int dtype, void* stream, float* sums_keep, int* deferred, const dreg_bn_extra* ex, double* self_keep)
 {
     hipStream_t st = (hipStream_t)stream;
     BnSplitkIn ski;
@@ -2099,6 +2338,7 @@ static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const flo
     const int rpc = bn_rows_per_chunk(V), nch = (V + rpc - 1) / rpc;
     const int CG = C / G, slabs = (CG + 255) / 256;
     if (bn_small_ok(B, V, C, G)) {
+        if (self_keep) return DREG_EINVAL;
         const dim3 g1(CG / BNS_COLS, B);
         float* sums = sums_keep ? sums_keep : coef;   // [B][C][2]: per-grid (sum g, sum g xhat)
 #define BNS_BWD(Tt, NRv) hipLaunchKernelGGL((bn_small_bwd_kernel<Tt, NRv>), g1, dim3(256), 0, st, (const Tt*)x, (const Tt*)dy, (const Tt*)y, scale_shift, mean_rstd, \
@@ -2114,6 +2354,7 @@ static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const flo
         return DREG_OK;
     }
     if (B > BN_MAX_GRIDS || slabs_ragged(CG)) return DREG_EINVAL;      // refused before anything is launched
+    if (self_keep && (!deferred || (g_bn_debug_skip & 2) || !dreg_bn_self_coef_supported(B, V, C, dtype))) return DREG_EINVAL;
     dim3 grid(nch, B, slabs);
     // residual + ReLU layers (the last BatchNorm of a bottleneck): the masked gradient the statistics pass forms IS the residual branch's
     // gradient — it is stored there, and the apply pass reads it back instead of dy and y (one activation-sized read less, same values)
@@ -2122,6 +2363,17 @@ static int bn3d_bwd_impl(const void* x, const void* dy, const void* y, const flo
     else if (dtype == 0) hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)y, mean_rstd, workspace, V, C, rpc, relu, scale_shift, g_stored ? (bf16_t*)dres : nullptr);
     else hipLaunchKernelGGL((bn_partial_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, (const float*)y, mean_rstd, workspace, V, C, rpc, relu, scale_shift, g_stored ? (float*)dres : nullptr);
     DREG_LAUNCH_CHECK();
+    if (self_keep) {      // self-coefficient form: c1 / c2 formed by the apply pass, dgamma / dbeta by the caller's batched tail over self_keep
+        const int rows = bn_self_rows(B, V, C, G);
+        const dim3 sgrid((V + rows - 1) / rows, B, bn_self_slabs(C, G));
+        if (dtype == 0) hipLaunchKernelGGL((bn_bwd_apply_self_kernel<bf16_t, 4>), sgrid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)y, workspace, mean_rstd, scale_shift,
+                                           (bf16_t*)dx, (bf16_t*)dres, self_keep, V, C, nch, rows, relu, g_stored);
+        else hipLaunchKernelGGL((bn_bwd_apply_self_kernel<float, 4>), sgrid, dim3(256), 0, st, (const float*)x, (const float*)dy, (const float*)y, workspace, mean_rstd, scale_shift,
+                                (float*)dx, (float*)dres, self_keep, V, C, nch, rows, relu, g_stored);
+        DREG_LAUNCH_CHECK();
+        *deferred = 1;
+        return DREG_OK;
+    }
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64 * (B < 8 ? B : 8)), 0, st, workspace, coef, dgamma, dbeta, B, nch, C, V, accumulate);
     DREG_LAUNCH_CHECK();
     const size_t tg = (size_t)B * V * CG;

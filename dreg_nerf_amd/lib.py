@@ -102,6 +102,11 @@ SIGNATURES = {
     "dreg_bn3d_bwd_defer_params": (I, [P] * 11 + [I, I, I, I, I, I, P, P, P]),
     "dreg_bn_running_update_batched": (I, [P, I, I, I, F, P]),
     "dreg_bn_param_grad_batched": (I, [P, I, I, I, I, P]),
+    "dreg_bn_self_coef_supported": (I, [I, I, I, I]),
+    "dreg_bn_self_coef_use": (I, [I, I, I, I, I]),
+    "dreg_bn_self_coef_rows": (I, [I, I, I, I]),
+    "dreg_bn3d_fwd_self_coef": (I, [P, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P, P, P]),
+    "dreg_bn3d_bwd_self_coef": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P]),
     "dreg_maxpool3d_fwd": (I, [P, P, P] + [I] * 9 + [P]),
     "dreg_maxpool3d_bwd": (I, [P, P, P] + [I] * 9 + [P]),
     "dreg_maxpool3d_bwd_acc": (I, [P, P, P] + [I] * 10 + [P]),
@@ -138,6 +143,7 @@ SIGNATURES = {
     "dreg_exec_destroy": (None, [P]),
     "dreg_exec_op_halo": (I, [P, I]),
     "dreg_exec_op_pointwise": (I, [P, I]),
+    "dreg_exec_op_bn_self_coef": (I, [P, I]),
     "dreg_exec_op_wgrad_grouped": (I, [P, I]),
     "dreg_exec_arena_bytes": (Z, [P]),
     "dreg_exec_pack_bytes": (Z, [P]),
@@ -330,6 +336,7 @@ PROBE_SIGNATURES = {
     "dreg_conv3_halo64_set": (None, [I]),
     "dreg_conv3_halo_set_prof": (None, [P]),
     "dreg_bn_set_small_max_voxels": (None, [I]),
+    "dreg_bn_set_self_wgs": (None, [I]),
     "dreg_ngp_set_rgb_chunks": (None, [I]),
     "dreg_ngp_set_density_unroll": (None, [I]),
     "dreg_ngp_set_xcd_levels": (None, [I]),
@@ -351,7 +358,7 @@ _probe_lib = None
 class ExecOpts(ctypes.Structure):
     """dreg_exec_opts of include/dreg_nerf.h (creation options of one trunk executor)."""
     _fields_ = [(n, c_int) for n in ("sparse_grads", "bn_batch_tails", "fuse_stem", "sparse_stem", "fold_res_bn", "fold_splitk", "group_wgrad",
-                                     "s2_accumulate", "fuse_bn_stats", "brick", "defer_head_pg", "persistent_deep", "guard", "pointwise_stream")] + [("reserved", c_int * 2)]
+                                     "s2_accumulate", "fuse_bn_stats", "brick", "defer_head_pg", "persistent_deep", "guard", "pointwise_stream", "bn_self_coef")] + [("reserved", c_int * 1)]
 
 
 SCENE_MAX_BLOCKS = 4

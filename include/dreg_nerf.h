@@ -276,6 +276,20 @@ int dreg_conv3d_igemm_defer(const void* in, const void* wt_packed, void* out, co
 int dreg_bn_small_in_regs(int B, int V, int C, int dtype);
 int dreg_bn_running_update_batched(const void* descs_dev, int n, int block_base, int nblocks, float momentum, void* stream);
 int dreg_bn_param_grad_batched(const void* descs_dev, int n, int block_base, int nblocks, int accumulate, void* stream);
+/* Self-coefficient forms of the large training-mode path: the apply pass forms scale / shift (forward) or c1 / c2 (backward) of its own channels
+ * from the chunk sums, so no finalize launch sits between the statistics and the apply pass (results bit-identical to dreg_bn3d_fwd_from_sums /
+ * dreg_bn3d_bwd).  The cross-grid tails are left to the two batched launches above: the per-grid fp64 pairs go to keep [B][C][2] — (mean, var)
+ * forward, (sum g, sum g xhat) backward — and a table record with a = NULL, b = keep names them.  dreg_bn_self_coef_supported: the form can
+ * run (else DREG_EINVAL); dreg_bn_self_coef_use: ... and it is the faster one for this shape (what the trunk executor's bn_self_coef option reads);
+ * dreg_bn_self_coef_rows: rows per workgroup of the apply pass (independent of the statistics chunking). */
+int dreg_bn_self_coef_supported(int B, int V, int C, int dtype);
+int dreg_bn_self_coef_use(int B, int V, int C, int dtype, int backward);
+int dreg_bn_self_coef_rows(int B, int V, int C, int dtype);
+int dreg_bn3d_fwd_self_coef(const void* x, const void* res, void* y, const float* gamma, const float* beta, float* scale_shift, float* mean_rstd,
+                            float* sums, int rows_per_chunk, int B, int V, int C, float eps, int relu, int dtype, double* keep,
+                            const float* res_scale_shift, void* stream);
+int dreg_bn3d_bwd_self_coef(const void* x, const void* dy, const void* y, const float* scale_shift, const float* mean_rstd,
+                            void* dx, void* dres, float* workspace, int B, int V, int C, int relu, int dtype, double* keep, void* stream);
 
 /* Stem fused (resnet3d.py:118-123: conv1 -> bn1 -> relu -> maxpool, bf16): pooled = maxpool3(relu(bn(x))) and its backward without the
  * full-resolution activation / gradient in between; pooled values and arg-max taps are bit-identical to dreg_bn3d_fwd + dreg_maxpool3d_fwd. */
@@ -442,7 +456,9 @@ typedef struct dreg_exec_opts {
                              synchronisation per op) and return DREG_EGUARD at the first op behind which a band has changed (dreg_exec_guard_last) */
     int pointwise_stream; /* 1 (default): dense 1^3 stride-1 convolutions (forward, data gradient, accumulating data gradient) that dreg_conv1_stream_use admits
                              run on csrc/conv_pointwise.hip (bit-identical); 0: the implicit GEMM */
-    int reserved[2];
+    int bn_self_coef;     /* 1 (default): large-path training BatchNorms that dreg_bn_self_coef_use admits run without finalize launches (dreg_bn3d_fwd_self_coef /
+                             _bwd_self_coef; their tails join the batched launches, so it needs bn_batch_tails; bit-identical); 0: three launches */
+    int reserved[1];
 } dreg_exec_opts;
 void dreg_exec_default_opts(dreg_exec_opts* o);
 void* dreg_exec_create_opts(const int* tensors, int nt, const int* ops, int nops, const int64_t* params, int np, const dreg_exec_opts* opts);
@@ -465,6 +481,7 @@ int dreg_exec_export_pack_table(void* h, void* host_out, int* host_row_desc, voi
 int dreg_exec_repack(void* h, const void* descs_dev, const int* row_desc_dev, void* stream);
 int dreg_exec_op_halo(void* h, int op);   /* bit 0 / 1: forward / data gradient of convolution `op` runs on the halo kernel (dreg_conv3_halo_use) */
 int dreg_exec_op_wgrad_grouped(void* h, int op);   /* 1: the weight gradient of convolution `op` is part of the grouped launch (group_wgrad) except under dreg_exec_set_timing, where it is launched and bracketed alone */
+int dreg_exec_op_bn_self_coef(void* h, int op);   /* bit 0 / 1: forward (when its chunk sums come from the producing convolution) / backward of BatchNorm `op` runs without a finalize launch (dreg_bn_self_coef_use) */
 int dreg_exec_op_pointwise(void* h, int op);   /* bit 0 / 1 / 2: forward / plain data gradient / accumulating data gradient of convolution `op` runs on the streaming 1^3 kernel (dreg_conv1_stream_use) */
 void dreg_exec_set_overlap(void* h, int enable);
 void dreg_exec_set_input_row_occupancy(void* h, const uint8_t* rowocc);   /* flags for the convolution that reads x_in (the stem); null = none */                             /* 1 (default): weight gradients on aux_stream */

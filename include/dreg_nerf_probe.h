@@ -36,6 +36,7 @@ void dreg_conv_set_glds_stages(int stages);          /* LDS pipeline stages of t
 void dreg_conv_set_wgrad_target_blocks(int blocks);   /* workgroups the automatic split choice aims for (default 384; 3072 until round 6) */
 /* largest per-grid volume (voxels) whose BatchNorm runs the fused statistics+apply kernels (default 512 = the 8^3 level; 16^3 measured slower fused); 0 = never */
 void dreg_bn_set_small_max_voxels(int v);
+void dreg_bn_set_self_wgs(int n);   /* self-coefficient BatchNorm apply passes: workgroup count above which the rows per workgroup double (default 512) */
 void dreg_sstem_set_pool_blocks(int n);              /* measurement: workgroups of the sparse stem's pooling launch (default 8192 = one pooled granule per thread at 8 x 32^3 x 64) */
 void dreg_voxel_set_own_sort(int on);                 /* experiment, default 0: 1 = the voxel keys of a downsample round (<= 131,072) are built, sorted (stable 4-bit LSD radix sort, ballot ranks) and segmented by ONE launch of one workgroup instead of rocPRIM radix_sort_pairs + inclusive_scan + three small kernels; identical results, but 0.45-1.45 ms per round on its single CU against ~0.07 ms (so the product path keeps rocPRIM) */
 void dreg_conv_set_bn_stats_epilogue(int on);        /* 0: dreg_conv3d_igemm_bnstats never emits sums (callers fall back to the BatchNorm's own statistics pass) */

@@ -23,6 +23,9 @@ def fpn(x, rows=None, *a, **kw):
     mark("fpn_fwd_start"); y = orig_fpn(x, rows, *a, **kw); mark("fpn_fwd_end"); return y
 model.fpn = fpn
 from dreg_nerf_amd import trunk_exec
+for i, a in enumerate(sys.argv):       # --opt bn_self_coef=0: a creation option of the trunk executor (dreg_exec_opts) for this run
+    if a == "--opt":
+        k, v = sys.argv[i + 1].split("="); trunk_exec.OPTS[k] = int(v)
 orig_bwd = trunk_exec.TrunkExecutor.backward
 def bwd(self, x, rows, g, generation=None):
     mark("fpn_bwd_start"); orig_bwd(self, x, rows, g, generation); mark("fpn_bwd_end")
